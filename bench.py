@@ -6,8 +6,19 @@ exact line search (two 𝒜 passes), R += αD, g! (S assembly + SpMM), norms, L-
 north-star instance of BASELINE.json configs[1]: MaxCut on G(n = 1e5, p = 2e-4), r = 32, FP64,
 h = 4, σ = σ₀ = 2 fixed, no early exit (gtol = 0, fprec = −∞), all state resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: set-up, pre-warm, W untimed steps, the K timed steps,
+the outputs if `--dump-outputs DIR` asks for them, the JSON line.  `--full` adds everything else the benchmark knows:
+the eager per-kernel profile and the dominant kernel's `roofline`, `cpu_baseline` (1 thread + all cores) with `parity`
+against the oracle, and `other_configs` (BASELINE configs 3–5); `--no-cpu-baseline` / `--no-other-configs` trim a
+`--full` run.  A failed parity makes a `--full` run exit 3.
+
+`--dump-outputs DIR` writes what the last timed step left behind, as a caller of the path receives it, to DIR/<name>.npy
+(float64): `state` = [ℒ, ‖grad‖, ‖primal_vio‖, last α, objective] (the returns of `inner_loop` and `var.obj`), `Rt` and
+`Gt` (n × r), `primal_vio_raw` and `y` (m + 1) — 53 MB on the north-star instance.  The instance, R₀ and every seed are
+fixed, so two builds run with the same arguments can be compared array for array.
 
 N > 1: independent replicas of the instance (graph seed + rank), one process per GPU, no data-path
 collective; RCCL only gathers the objectives at the end.  value = N·K / max-over-ranks time.
@@ -45,8 +56,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs block (configs 3–5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step left to DIR/<name>.npy (rank 0's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: eager per-kernel profile + roofline, cpu_baseline + parity, other_configs (configs 3–5)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and parity")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other_configs block (configs 3–5)")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="launcher/collective self-test WITHOUT a GPU: gloo + the CPU checker on a small instance; "
                          "exercises spawn, rendezvous, barrier, max-over-ranks and the gather — not a measurement")
@@ -66,6 +81,10 @@ def launch_children(args) -> int:
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps),
            "--warmup", str(args.warmup)]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+    if args.full:
+        cmd.append("--full")
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.no_other_configs:
@@ -146,12 +165,13 @@ def algorithmic_bytes(d, h):
     return per_kernel, b_iter
 
 
-def run_fixed(var, normC, normb, state, iters):
-    """`iters` inner iterations at fixed σ with every exit test disabled except the iteration budget."""
-    out = var.inner_loop(normC, normb, True, True, False, 0.0, -1e300, iters, 0.0, *state)
+def run_fixed(var, normC, normb, state, iters, whole=False):
+    """`iters` inner iterations at fixed σ with every exit test disabled except the iteration budget.
+    → (ℒ, ‖grad‖, ‖primal_vio‖), the state the next call takes; `whole`: everything `inner_loop` returns."""
+    out = var.inner_loop(normC, normb, True, True, False, 0.0, -1e300, iters, 0.0, *state[:3])
     if out[4] != iters:
         raise RuntimeError(f"inner loop stopped after {out[4]} of {iters} iterations (exit {out[5]})")
-    return out[:3]
+    return out if whole else out[:3]
 
 
 def first_iterations(sj, abi, data, r, n_iters):
@@ -170,6 +190,17 @@ def parity_ok(parity, gpu_first, cpu_first, tol=1e-8) -> bool:
     it is itself at round-off level, where a relative error means nothing."""
     pv_ok = parity["rel_pv"] < tol or abs(gpu_first[2] - cpu_first[2]) < tol
     return bool(max(parity["rel_L"], parity["rel_grad"], parity["rel_obj"]) < tol and pv_ok)
+
+
+def dump_outputs(out_dir, var, last):
+    """What the last timed step left, as a caller of the path receives it: the returns of `inner_loop` with the objective,
+    and the solver state it reads back — each as <name>.npy, float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"state": np.array(list(last[:4]) + [var.obj], dtype=np.float64),
+              "Rt": var.Rt, "Gt": var.Gt, "primal_vio_raw": var.primal_vio_raw, "y": var.y}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def effective_cpus() -> int:
@@ -300,7 +331,8 @@ def main():
     data = problems.maxcut_data(problems.gnp_graph(n_nodes, p_edge, GRAPH_SEED + rank))
     normC, normb = data.normC(), float(np.linalg.norm(data.b))
 
-    # the first PARITY_ITERS iterations from R₀, kept for the comparison with the oracle's (cpu_baseline)
+    # the first PARITY_ITERS iterations from R₀: part of the set-up in every run (the timed steps start from the same
+    # state with and without --full), kept for the comparison with the oracle's (cpu_baseline, --full)
     var, gpu_first = first_iterations(sj, abi, data, rank_r, PARITY_ITERS)
     dims = var.dims()
     h = var.h
@@ -317,22 +349,26 @@ def main():
 
     barrier()
     t0 = time.perf_counter()
-    state = run_fixed(var, normC, normb, state, K)      # timed region: hipGraph batches, no events
+    state = run_fixed(var, normC, normb, state, K, whole=True)   # timed region: hipGraph batches, no events
     abi.device_synchronize()                            # this rank's K steps are complete here …
     dt = time.perf_counter() - t0
     barrier()                                           # … the closing barrier brackets the region; the MAX over ranks of
                                                         # dt (below) is the time until the slowest rank was done
     obj = var.obj
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, var, state)
 
-    # Per-kernel device time: the same iteration stream replayed eagerly right after the timed
+    # Per-kernel device time (--full): the same iteration stream replayed eagerly right after the timed
     # region with a hipEvent pair around every launch, on the solver's own stream (events cannot
     # bracket individual nodes of a graph replay).  rocprofv3 --kernel-trace of this command
     # (profiles/) measures the kernels of the timed region itself and must agree.
     P = min(K, 50)
-    var.profile_enable(True)
-    state = run_fixed(var, normC, normb, state, P)
-    prof_all = var.profile()
-    var.profile_enable(False)
+    prof_all = {}
+    if args.full:
+        var.profile_enable(True)
+        state = run_fixed(var, normC, normb, state, P)
+        prof_all = var.profile()
+        var.profile_enable(False)
     if prof_all.get("fast_step", (0, 0.0))[0] and not prof_all.get("lbfgs_update", (0, 0.0))[0]:
         # lbfgs_update! rides the step kernel (k_fast_step2<…,4>): charged the fused dataflow's compulsory bytes,
         # and the in-loop direction kernel no longer parks y_next
@@ -373,29 +409,33 @@ def main():
             "bytes_per_iteration_algorithmic": b_iter,
             "bytes_per_iteration_note": "SURVEY §8d: the reference's UNFUSED operator sequence (27N + sparse); "
                                         "the fused kernels below are charged their own compulsory bytes",
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved,
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "traffic": load_traffic(dominant),
-                         "algorithmic_bytes_per_launch": per_kernel_bytes[dominant],
-                         "avg_launch_us": 1e6 * avg_s, "launches_timed": launches,
-                         # (the PMC bytes the kernel really moves over the same duration: what the memory system is doing)
-                         "traffic_GBps": (load_traffic(dominant) or 0) / avg_s / 1e9 if avg_s > 0 else None,
-                         "note": ("fast_step on the ring form of the L-BFGS history is charged R, D, W, G_old in and R, G out (6N): "
-                                  "s_j, y_j are not stored; the 6N of history its Gram dots re-read are this design's choice"
-                                  if dominant == "fast_step" and stats.get("ring_history_loops", 0) > 0 else None)},
             "iteration_roofline": {"achieved": b_iter * (K / dt_max) / 1e9, "peak": HBM_PEAK_GBPS,
                                    "unit": "GB/s", "frac": b_iter * (K / dt_max) / 1e9 / HBM_PEAK_GBPS},
-            "kernels_eager_profile": kern,
             "objectives": objs,
             "per_rank": {"seconds": dts, "iterations_per_s": [K / t for t in dts],
                          "slowest_over_fastest": max(dts) / min(dts)},
             "library_stats": stats,
         }
+        if args.full:       # what the eager replay measured: the dominant kernel against the HBM roofline, and every kernel
+            line["roofline"] = {
+                "bound": "hbm", "kernel": dominant, "achieved": achieved,
+                "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                "traffic": load_traffic(dominant),
+                "algorithmic_bytes_per_launch": per_kernel_bytes[dominant],
+                "avg_launch_us": 1e6 * avg_s, "launches_timed": launches,
+                # (the PMC bytes the kernel really moves over the same duration: what the memory system is doing)
+                "traffic_GBps": (load_traffic(dominant) or 0) / avg_s / 1e9 if avg_s > 0 else None,
+                "note": ("fast_step on the ring form of the L-BFGS history is charged R, D, W, G_old in and R, G out (6N): "
+                         "s_j, y_j are not stored; the 6N of history its Gram dots re-read are this design's choice"
+                         if dominant == "fast_step" and stats.get("ring_history_loops", 0) > 0 else None)}
+            line["kernels_eager_profile"] = kern
         if selftest:
             line["selftest"] = True
             line["config"]["workload"] = (f"SELF-TEST (no GPU): MaxCut G({n_nodes},{p_edge}) r={rank_r} on the CPU "
                                           "checker over gloo — exercises the launcher and the collectives only")
-        elif world == 1 and not args.no_cpu_baseline:
+        elif not args.full or args.no_cpu_baseline:
+            pass        # a plain run ends with its headline figure
+        elif world == 1:
             line["cpu_baseline"], line["parity"] = cpu_baseline(sj, data, rank_r, gpu_first)
             if not line["parity"]["ok"]:
                 print(f"bench.py: PARITY FAILED against the oracle: {line['parity']}", file=sys.stderr)
@@ -408,7 +448,7 @@ def main():
                 if bad:
                     print(f"bench.py: PARITY FAILED against the oracle in {bad}", file=sys.stderr)
                     rc = 3
-        elif world > 1 and not selftest and not args.no_cpu_baseline:
+        else:
             # rank 0 still compares its first iterations with the oracle (one thread, ≈ 10 s): cheap, and a wrong result on
             # a multi-GPU node should not pass for a fast one
             from oracle import oracle

@@ -1,9 +1,10 @@
 #!/bin/bash
 # dev tool: rocprofv3 kernel trace of a short bench run; prints per-kernel median / mean durations
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/ktrace
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats -d $OUT -o t --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps ${1:-200} --warmup 20 --no-cpu-baseline > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT -o t --output-format csv -- python3 $ROOT/bench.py --steps ${1:-200} --warmup 20 --full --no-cpu-baseline > $OUT/bench.log 2>&1
 tail -c 300 $OUT/bench.log | head -c 0
 python3 - "$OUT" <<'PY'
 import sys, glob, csv, collections, statistics
