@@ -669,8 +669,10 @@ k_lbfgs_dir_ring(const DevCtrl* __restrict__ c, FactorArena A, long long N, int 
 // Ring form → stored form, in place: every element's 2h + 2 ring values are loaded before any of them is overwritten.
 // G ← the current gradient; s_j ← α_j·D, y_j ← G' − G for the pairs in ring form (the older ones are in their slots as
 // stored: untouched); after a step without lbfgs_update! (unc: the relative-decrease exit) the slot lbfgs_dir! had claimed
-// holds y = −G_old (src/lbfgs.jl:121-123) and dirt the unscaled direction.  Otherwise dirt is left to the lazy copy dirt ←
-// s_latest.  Arrays by physical index: 0 = G / dirt, 1 + j = history slot j.
+// holds y = −G_old (src/lbfgs.jl:121-123) and dirt the unscaled direction; unc = 2: the loop left through the line search's
+// "not a descent direction" error — the direction stands at position ring_k, no step was taken, G is still the one at ring_k
+// and the claimed slot holds y = −G all the same.  Otherwise dirt is left to the lazy copy dirt ← s_latest.  Arrays by
+// physical index: 0 = G / dirt, 1 + j = history slot j.
 template <int HM>
 __global__ void __launch_bounds__(SDPLR_NT)
 k_ring_materialize(FactorArena A, long long N, int h, int rk, int rn, int unc, int latest, int j0, const DevCtrl* __restrict__ c) {
@@ -696,7 +698,7 @@ k_ring_materialize(FactorArena A, long long N, int h, int rk, int rn, int unc, i
     gp[q] = (q == 0 || q > h) ? aslot(A, AS_G) : aslot(A, as_y0(A) + q - 1);
     dp[q] = (q == 0 || q > h) ? aslot(A, AS_D) : aslot(A, AS_S0 + q - 1);
   }
-  const int qcur = phys(unc ? ring_back(rk, -1, h) : rk), qold = phys(rk);
+  const int qcur = phys(unc == 1 ? ring_back(rk, -1, h) : rk), qold = phys(rk);
   const long long stride = (long long)gridDim.x * SDPLR_NT;
   for (long long i = (long long)blockIdx.x * SDPLR_NT + threadIdx.x; i < N; i += stride) {
     double gv[HM + 1], dv[HM + 1];

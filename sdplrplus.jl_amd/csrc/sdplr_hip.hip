@@ -3096,6 +3096,23 @@ int enq_resident_loop(S* s, double time_budget_s, bool refresh_P, bool pre_lambd
   return SDPLR_OK;
 }
 
+// The "not a descent direction" exit (src/linesearch.jl:60-62) leaves the loop behind lbfgs_dir! and in front of everything
+// else: R and G untouched, dirt the unscaled direction, and slot latest mod h holding y_next = −G (src/lbfgs.jl:121-123) —
+// which the next lbfgs_dir! reads as that pair's y.  The kernels that fuse lbfgs_update! leave y_next to the step kernel,
+// which did not run: it is parked here, and the Gram rows are recomputed from the stored vectors by whoever needs them next.
+// (A history in ring form parks it when it is turned back into the stored form: k_ring_materialize, unc = 2.)
+static int park_ynext_after_not_descent(S* s, int latest) {
+  s->sg_stale = true;
+  if (s->h == 0) return SDPLR_OK;
+  s->ynext_pending = true;
+  if (s->ring_on) return SDPLR_OK;
+  const int nb = blocks_for(s->N, SDPLR_NT, 2048);
+  k_ring_dirt<<<nb, SDPLR_NT, 0, s->stream>>>(aslot(s->arena, as_y0(s->arena) + latest % (int)s->h), aslot(s->arena, AS_G), s->N, -1.0);
+  HIPCK(s, hipGetLastError());
+  HIPCK(s, hipStreamSynchronize(s->stream));
+  return SDPLR_OK;
+}
+
 // launch + wait + the host-side bookkeeping of one resident loop (the control block has been pushed by the caller);
 // pre_lambda / pre_clear_fg: the head of a major iteration rides the same launch (sdplr_hip_major_iteration)
 int run_resident_loop(S* s, double time_budget_s, bool pre_lambda, bool pre_clear_fg, double* Lio, double* gnio, double* pnio,
@@ -3138,8 +3155,10 @@ int run_resident_loop(S* s, double time_budget_s, bool pre_lambda, bool pre_clea
   s->sg_stale = (why_rs == EXIT_RELDELTA);
   s->ynext_pending = (why_rs == EXIT_RELDELTA) && s->h > 0;
   if (c->err == SDPLR_ERR_NOT_DESCENT) {
+    const int latest_ = c->latest;
     c->err = 0; c->done = 0;
     (void)push(s);
+    if ((rc = park_ynext_after_not_descent(s, latest_))) return rc;
     return fail(s, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
   }
   s->st_iters += c->iters;
@@ -3673,7 +3692,7 @@ int32_t sdplr_hip_update_lambda(S* s) {
 static int ring_drop_for_clear(S* s) {
   if (!s || !s->finalized || !s->ring_on) return SDPLR_OK;
   const int h = (int)s->h, rk = s->ring_k, j0 = s->ring_j0;
-  const int pG = s->ring_unc ? ring_back(rk, -1, h) : rk;
+  const int pG = s->ring_unc == 1 ? ring_back(rk, -1, h) : rk;   // (2: the not-descent exit, no step taken)
   if (pG != 0) HIPCK(s, hipMemcpyAsync(aslot(s->arena, AS_G), ring_G(s->arena, pG, j0), s->N * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
   const int nb = blocks_for(s->N, SDPLR_NT, 2048);
   if (s->dirt_from >= 0 && s->ring_n >= 1) {        // s_latest = α·D of the newest ring pair
@@ -3879,11 +3898,21 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
       memset(c->ring_alpha, 0, sizeof c->ring_alpha);
     }
     c->ring_on = s->ring_now ? 1 : 0;
-    s->ring_on = s->ring_now;
     // (the control block went to the device above, before the route was known: the ring's scalars follow it)
     if (fresh || was != c->ring_on)
       HIPCK(s, hipMemcpyAsync(&s->ctrl->ring_on, &c->ring_on, sizeof(DevCtrl) - offsetof(DevCtrl, ring_on), hipMemcpyHostToDevice, s->stream));
+    s->ring_on = s->ring_now;
   }
+  // From here to the closing pull the handle's ring scalars (ring_k … ring_alpha) are those of an EARLIER ring, or zeros: a
+  // return in between must not leave the handle claiming ring form — the next look would materialise from them.  No valid
+  // control block exists on such a return (a HIP call failed): the arena is taken as it lies, the Gram data as unknown.
+  auto bail = [&](int rc_) {
+    s->ring_on = false;
+    s->gram_dirty = true;
+    s->G_consistent = false;
+    s->hc_valid = false;
+    return rc_;
+  };
   const int ar = use_armijo ? 1 : (s->ring_now ? (s->pdrop_now ? 3 : 4) : (s->pdrop_now ? 2 : 0));
   const bool edgep = !fastp && edge_applies(s, use_armijo);
   auto enq_iter = [&]() {
@@ -3993,8 +4022,8 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
         enq_iter();
         s->prof_on = true;
       }
-      HIPCK(s, hipGetLastError());
-      if ((rc = pull(s))) return rc;
+      if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return bail(fail(s, SDPLR_ERR_HIP, std::string("inner_loop: ") + hipGetErrorString(e_)));
+      if ((rc = pull(s))) return bail(rc);
       if (c->done) break;
       if (time_budget_s > 0 &&
           std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > time_budget_s) {
@@ -4004,12 +4033,12 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
     }
   } else {
     int cur = 0;
-    if ((rc = launch_batch(cur))) return rc;
+    if ((rc = launch_batch(cur))) return bail(rc);
     for (;;) {
       const bool more = !plan_closed;
-      if (more && (rc = launch_batch(cur ^ 1))) return rc;  // speculative: queued behind batch `cur`
+      if (more && (rc = launch_batch(cur ^ 1))) return bail(rc);  // speculative: queued behind batch `cur`
       const double tw = now();
-      HIPCK(s, hipEventSynchronize(s->snap_ev[cur]));
+      if (hipError_t e_ = hipEventSynchronize(s->snap_ev[cur]); e_ != hipSuccess) return bail(fail(s, SDPLR_ERR_HIP, std::string("inner_loop: ") + hipGetErrorString(e_)));
       t_wait += now() - tw;
       if (s->snap[cur]->done) {
         // (usable as the final state only if nothing was enqueued behind it — no speculative batch — and it was taken
@@ -4037,14 +4066,20 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
     s->hc_valid = true;
   } else {
     enq_boundary(s, 0, 1, 0, 0);
-    if ((rc = pull(s))) return rc;
+    if ((rc = pull(s))) return bail(rc);
+  }
+  // the ring as the loop left it (ensure_canonical / lbfgs_clear work from these): taken straight from the closing control
+  // block, in front of every return below — the error exit leaves a ring too
+  if (s->ring_now) {
+    s->ring_k = c->ring_k; s->ring_n = c->ring_n; s->ring_unc = c->ring_unc; s->ring_latest = c->latest; s->ring_j0 = c->ring_j0;
+    memcpy(s->ring_alpha, c->ring_alpha, sizeof s->ring_alpha);
   }
   if (c->done) why = c->exit_reason;   // the device's verdict wins over the host's time check
   if (loop_fused && c->iters > 0 && c->err == 0 && why != EXIT_RELDELTA) {
     // the kernels lbfgs_update! rides on leave `dirt *= α` (src/lbfgs.jl:142) to a copy dirt ← s_latest, made when
     // something looks at dirt (ensure_dirt)
     s->dirt_from = c->latest - 1;
-  } else if (c->iters == 0) {
+  } else if (c->iters == 0 && c->err == 0) {
     s->dirt_from = dirt_was_from;   // not one iteration ran: dirt is what it was
   }
   if (dbg)
@@ -4055,19 +4090,21 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
   s->sg_stale = (why == EXIT_RELDELTA);
   s->ynext_pending = (why == EXIT_RELDELTA) && s->h > 0;
   if (c->err == SDPLR_ERR_NOT_DESCENT) {
+    const int latest_ = c->latest;
     c->err = 0; c->done = 0;
     (void)push(s);
+    // lbfgs_dir! ran, the step did not: on a ring the direction lies at position ring_k (unc = 2: k_ring_materialize)
+    if (s->ring_now) { s->st_ring_loops++; s->ring_unc = 2; }
+    s->P_age += c->iters;
+    s->G_age = s->pdrop_now ? s->G_age + c->iters : 0;
+    if ((rc = park_ynext_after_not_descent(s, latest_))) return rc;
     return fail(s, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
   }
   s->st_iters += c->iters;
   s->P_age += c->iters;
   s->G_age = s->pdrop_now ? s->G_age + c->iters : 0;   // (the P-based kernels form G from P and y at every step)
   if (s->pdrop_now) s->st_pdrop++;
-  if (s->ring_now) {   // the ring as the loop left it (ensure_canonical / lbfgs_clear work from these)
-    s->st_ring_loops++;
-    s->ring_k = c->ring_k; s->ring_n = c->ring_n; s->ring_unc = c->ring_unc; s->ring_latest = c->latest; s->ring_j0 = c->ring_j0;
-    memcpy(s->ring_alpha, c->ring_alpha, sizeof s->ring_alpha);
-  }
+  if (s->ring_now) s->st_ring_loops++;
   s->G_consistent = true;                              // g! has run at the loop's last point
   *Lio = c->L; *gnio = c->gnorm; *pnio = c->pvnorm;
   if (last_alpha) *last_alpha = c->alpha;
@@ -4805,14 +4842,23 @@ int32_t sdplr_hip_batch_major_iteration(int32_t count, sdplr_hip_major_item* it)
         const size_t res_off = batch_up(xch_off + xch_bytes);
         if (xch_bytes) memset(bb.host + xch_off, 0, xch_bytes);
         size_t lds = 0;
+        int rc_pre = SDPLR_OK;   // (the launch is shared: an item that cannot be prepared fails the group, as a failed launch does)
         for (size_t k = 0; k < nb; k++) {
-          const sdplr_hip_major_item& q = it[idx[lo + k]];
+          sdplr_hip_major_item& q = it[idx[lo + k]];
           S* sk = q.s;
           sk->hc_valid = false;
-          if (sk->dirt_from >= 0) {   // (an instance that came over from the multi-launch route with dirt ← s_latest pending)
-            if (ensure_dirt(sk) == SDPLR_OK) (void)hipStreamSynchronize(sk->stream);
-          }
           const bool resume = q.update_lambda == SDPLR_MAJOR_RESUME;
+          // an instance that came over from the multi-launch route: its history may be in ring form (the kernel clears the
+          // history and writes G at its own place — the ring goes, as in sdplr_hip_major_iteration; a resumed loop reads the
+          // stored pairs) and dirt ← s_latest may be pending
+          const bool came_over = sk->ring_on || sk->dirt_from >= 0;   // (work on the handle's own stream: waited for below)
+          int rc_k = resume ? ensure_canonical(sk) : ring_drop_for_clear(sk);
+          if (!rc_k && sk->dirt_from >= 0) rc_k = ensure_dirt(sk);
+          if (!rc_k && came_over && hipStreamSynchronize(sk->stream) != hipSuccess) rc_k = fail(sk, SDPLR_ERR_HIP, "batch_major_iteration: preparing an instance");
+          if (rc_k) {
+            q.status = rc_k;
+            if (!rc_pre) { rc_pre = rc_k; if (sk != s) s->err = sk->err; }
+          }
           if (!resume) sk->sg_stale = sk->ynext_pending = false;   // (cleared history: see sdplr_hip_lbfgs_clear)
           RsLoopArgs a = resume ? rs_loop_args(sk, q.time_budget_s, !sk->P_valid, false, false)
                                 : rs_loop_args(sk, q.time_budget_s, true, q.update_lambda != 0, true);
@@ -4830,7 +4876,7 @@ int32_t sdplr_hip_batch_major_iteration(int32_t count, sdplr_hip_major_item* it)
           lds = std::max(lds, rs_loop_lds(sk));
         }
         const RsLoopArgs* dtab = reinterpret_cast<const RsLoopArgs*>(bb.dev);
-        int rc = batch_round_trip(s, bb, g_w > 1 ? xch_off + xch_bytes : nb * sizeof(RsLoopArgs), res_off, nb * 8 * sizeof(double), [&](hipStream_t st) {
+        int rc = rc_pre ? rc_pre : batch_round_trip(s, bb, g_w > 1 ? xch_off + xch_bytes : nb * sizeof(RsLoopArgs), res_off, nb * 8 * sizeof(double), [&](hipStream_t st) {
           if (g_w > 1) { RS_VEC_DISPATCH(s, ({ RS_SET_ATTR((k_rs_team_batch<VEC, 4>)); k_rs_team_batch<VEC, 4><<<8 * g_w * (((int)nb + 7) / 8), SDPLR_RS_NT, lds, st>>>(dtab, (int)nb, g_w); })) }
           else if (g_pd) { RS_VEC_DISPATCH(s, ({ RS_SET_ATTR((k_rs_loop_batch<VEC, 4, true>)); k_rs_loop_batch<VEC, 4, true><<<(int)nb, SDPLR_RS_NT, lds, st>>>(dtab); })) }
           else { RS_VEC_DISPATCH(s, ({ RS_SET_ATTR((k_rs_loop_batch<VEC, 4, false>)); k_rs_loop_batch<VEC, 4, false><<<(int)nb, SDPLR_RS_NT, lds, st>>>(dtab); })) }
@@ -4868,6 +4914,7 @@ int32_t sdplr_hip_batch_major_iteration(int32_t count, sdplr_hip_major_item* it)
           if (err == SDPLR_ERR_NOT_DESCENT) {
             int r2 = pull(sk);
             if (!r2) { sk->hc->err = 0; sk->hc->done = 0; r2 = push(sk); }
+            if (!r2) r2 = park_ynext_after_not_descent(sk, sk->hc->latest);
             q.status = r2 ? r2 : fail(sk, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
             continue;
           }

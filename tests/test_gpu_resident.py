@@ -227,8 +227,10 @@ def test_resident_loop_takes_the_steepest_descent_fallback(hip_abi, oracle_abi, 
     g.close(); o.close()
 
 
-def test_resident_loop_is_run_to_run_deterministic_and_reports_not_descent(hip_abi):
-    data = problems.maxcut_data(problems.gnp_graph(300, 0.05, 7))
+def test_resident_loop_is_run_to_run_deterministic(hip_abi):
+    """Three fresh handles, 40 iterations in one launch each: R, G and ℒ bit for bit.  (The "not a descent direction" exit of
+    this loop, on this instance: test_gpu_handover.py::test_not_descent_exit_on_the_resident_routes.)"""
+    data =problems.maxcut_data(problems.gnp_graph(300, 0.05, 7))
     normC, normb = data.normC(), float(np.linalg.norm(data.b))
     seen = set()
     for rep in range(3):

@@ -321,3 +321,85 @@ def test_experiment_builders(oracle_abi, name):
     var.g()
     assert np.max(np.abs(var.Gt - 2 * S_dense(C, As, var.y) @ var.Rt)) < 1e-10 * (1 + np.max(np.abs(var.Gt)))
     var.close()
+
+
+# ---- the oracle halves of tests/test_gpu_handover.py: the instances and what the oracle does on them, pinned without a GPU ----
+def test_hp_gradient_agrees_with_the_oracle_on_the_reference_grid(oracle_abi):
+    """helpers.hp_gradient (dense, np.longdouble; math.fsum over exact products where longdouble is a double) against the
+    oracle's g! on the reference's unit-test grid, MaxCut and MinBisection.  Largest relative difference found (∞-norm over
+    the entries, relative to the largest entry): 3.6e-16 — the oracle's own FP64 rounding; asserted at four times that."""
+    import helpers
+    worst = 0.0
+    for family in ("maxcut", "minimum_bisection"):
+        for seed, n, p, r in helpers.GRID:
+            data, C, As, bs = helpers.make_data(family, seed, n, p)
+            o, _ = helpers.make_solver(oracle_abi, data, r, seed=seed)
+            o.fg(data.normC(), float(np.linalg.norm(data.b)))
+            o.g()
+            G_hp = helpers.hp_gradient(C, As, bs, o.Rt, o.λ, o.σ)
+            worst = max(worst, float(np.max(np.abs(o.Gt - G_hp)) / np.max(np.abs(G_hp))))
+            # … and S(y) of the oracle's own y is the S the helper forms: y = −(λ − σ·v)
+            S = helpers.S_dense(C, As, o.y)
+            assert np.max(np.abs(2 * S @ o.Rt - np.asarray(G_hp, dtype=np.float64))) < 1e-12 * (1 + np.max(np.abs(o.Gt)))
+            o.close()
+    assert worst < 1.5e-15, worst
+
+
+def test_hp_gradient_without_extended_precision(oracle_abi, monkeypatch):
+    """The math.fsum branch (taken where np.longdouble has no more than 53 bits) against the extended-precision one."""
+    import helpers
+    data, C, As, bs = helpers.make_data("minimum_bisection", 3, 12, 0.4)
+    o, _ = helpers.make_solver(oracle_abi, data, 3, seed=3)
+    o.fg(data.normC(), float(np.linalg.norm(data.b)))
+    wide = helpers.hp_gradient(C, As, bs, o.Rt, o.λ, o.σ)
+    real = np.finfo     # (where np.longdouble is a double already, both calls take the fsum branch)
+    monkeypatch.setattr(np, "finfo", lambda t: real(np.float64) if t is np.longdouble else real(t))
+    narrow = helpers.hp_gradient(C, As, bs, o.Rt, o.λ, o.σ)
+    monkeypatch.undo()
+    assert narrow.dtype == np.float64
+    assert float(np.max(np.abs(narrow - wide)) / np.max(np.abs(wide))) < 4 * 2.0 ** -53
+    o.close()
+
+
+@pytest.mark.parametrize("route,k1", [("launches", 6), ("launches", 9), ("resident", 6), ("resident", 9)])
+def test_not_descent_recipe_on_the_oracle(oracle_abi, route, k1):
+    """fg!, k1 iterations, G ← −G, a loop: refused with code −3 ("cubic[1] should be less than 0"), R bit-unchanged, G as
+    written, y_next = −G parked by lbfgs_dir! (src/lbfgs.jl:121-123); fg! + 5 iterations then run to their budget."""
+    import helpers
+    data, r, seed = helpers.not_descent_instance(route)
+    nC, nb = data.normC(), float(np.linalg.norm(data.b))
+    o, _ = helpers.make_solver(oracle_abi, data, r, seed=seed, h=4)
+    out = o.inner_loop(nC, nb, True, True, False, 0.0, -1e300, k1, 0.0, *o.fg(nC, nb))
+    assert out[4] == k1 and out[5] == 2
+    G, R = o.Gt, o.Rt
+    o.set_factor(cabi.F_GT, -G)
+    with pytest.raises(cabi.SdplrError, match=r"cubic\[1\] should be less than 0") as ei:
+        o.inner_loop(nC, nb, True, True, False, 0.0, -1e300, 5, 0.0, *out[:3])
+    assert ei.value.code == cabi.ERR_NOT_DESCENT == -3
+    assert np.array_equal(o.Rt, R) and np.array_equal(o.Gt, -G)
+    latest = int(o.get_scalar(cabi.S_LBFGS_LATEST))
+    assert latest == (k1 - 1) % 4 + 1
+    assert np.array_equal(o.get_factor(cabi.F_LBFGS_Y + latest % 4), G)
+    out = o.inner_loop(nC, nb, True, True, False, 0.0, -1e300, 5, 0.0, *o.fg(nC, nb))
+    assert out[4] == 5 and out[5] == 2 and np.all(np.isfinite(out[:4])) and out[3] > 0
+    o.close()
+
+
+def test_long_carry_recipe_on_the_oracle(oracle_abi):
+    """MaxCut on G(600, 8/600), r = 32, h = 4, gtol 0, fprec −1e300: still moving at iteration 512 (α ≈ 0.09, relative
+    ‖G‖ ≈ 2e-7); of 1000 iterations the first 573 move, then the line search returns α = 0 and the same finite (ℒ, ‖G‖, ‖pv‖)
+    comes back to the end of the budget; one iteration per call is the single call bit for bit."""
+    import helpers
+    data, C, As, bs, r, seed = helpers.long_carry_instance()
+    nC, nb = data.normC(), float(np.linalg.norm(data.b))
+    o, _ = helpers.make_solver(oracle_abi, data, r, seed=seed, h=4)
+    out = o.inner_loop(nC, nb, True, True, False, 0.0, -1e300, 512, 0.0, *o.fg(nC, nb))
+    assert out[4] == 512 and out[5] == 2 and 0.05 < out[3] < 0.2 and 1e-8 < out[1] < 1e-6
+    mid = out
+    out = o.inner_loop(nC, nb, True, True, False, 0.0, -1e300, 488, 0.0, *out[:3])
+    assert out[4] == 488 and out[5] == 2 and out[3] == 0.0 and np.all(np.isfinite(out[:3]))
+    assert np.all(np.isfinite(o.Rt)) and np.all(np.isfinite(o.Gt))
+    moving, last = helpers.oracle_moving_iterations(oracle_abi, 1000)
+    assert moving == 573
+    assert last[:4] == out[:4] and mid[0] > last[0]
+    o.close()
