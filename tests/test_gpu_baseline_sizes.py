@@ -37,6 +37,39 @@ def _instance(which):
     raise KeyError(which)
 
 
+def _sparse_S_and_tau(data, y, q):
+    """(S without its rank-one term as CSR, c of the rank-one term c·11ᵀ, τ) for S = Σ yᵢAᵢ + y_C·C assembled from the batched
+    constraint set.  τ = q·γ·A as in helpers.whole_run_checks: γ = 4·(d + ⌈log₂ n⌉ + 8)·2⁻⁵³ with d the longest row (n with a
+    rank-one term), A = ‖|S|‖∞ — with the rank-one term row i of |S| sums to Σ_{j in the row's pattern}(|S_ij + c| − |c|) + n·|c|."""
+    n, b = data.n, data.sparse
+    w = np.repeat(np.asarray(y)[b.global_inds], np.diff(b.ent_ptr))
+    Ssp = sp.coo_matrix((b.V * w, (b.I, b.J)), shape=(n, n)).tocsr()
+    Ssp.sum_duplicates()
+    c = 0.0
+    for gid, M in data.lowrank:
+        assert M.B.shape[1] == 1 and np.all(M.B == 1.0)
+        c += y[gid] * M.D[0]
+    shifted = Ssp.copy()
+    shifted.data = np.abs(shifted.data + c) - abs(c)
+    A = float(np.max(np.asarray(shifted.sum(axis=1)).ravel() + n * abs(c)))
+    d = n if data.lowrank else int(np.max(np.diff(Ssp.indptr)))
+    gamma = 4.0 * (d + int(np.ceil(np.log2(n))) + 8) * 2.0 ** -53
+    return Ssp, c, q * gamma * A
+
+
+def _lambda_min_and_tau(data, y, q):
+    """(λ_min(S), τ, ‖S·z − λ·z‖): scipy's eigsh for the smallest eigenvalue of the sparse S plus its rank-one term as a
+    LinearOperator, run to a residual far below τ (the caller asserts it)."""
+    import scipy.sparse.linalg as sla
+    n = data.n
+    Ssp, c, tau = _sparse_S_and_tau(data, y, q)
+    op = sla.LinearOperator((n, n), matvec=lambda x: Ssp @ x + c * np.sum(x), dtype=np.float64)
+    vals, vecs = sla.eigsh(op, k=1, which="SA", tol=1e-12, ncv=48, maxiter=20000,
+                           v0=np.random.Generator(np.random.PCG64(17)).standard_normal(n))
+    z = vecs[:, 0]
+    return float(vals[0]), tau, float(np.linalg.norm(op.matvec(z) - vals[0] * z))
+
+
 @pytest.mark.parametrize("which", ["maxcut_n1e5", "lovasz_chunglu_5e4", "minbis_n1e5"])
 def test_first_iterations_match_oracle_at_baseline_size(hip_abi, oracle_abi, which):
     data, seed = _instance(which)
@@ -58,7 +91,7 @@ def test_first_iterations_match_oracle_at_baseline_size(hip_abi, oracle_abi, whi
         s.dual_obj(float(data.n), 0, out["v0"])                 # copy2y + 𝒜t_preprocess! (:384-385) + Lanczos
         al, be, k = s.lanczos(q, out["v0"])
         assert k == q
-        out[name].update(lz_alpha=al, lz_beta=be, q=q, ritz=s.tridiag_mineig(al, be))
+        out[name].update(lz_alpha=al, lz_beta=be, q=q, ritz=s.tridiag_mineig(al, be), y_S=s.y)
         s.close()
     h, o = out["hip"], out["oracle"]
     assert np.allclose(h["fg"], o["fg"], rtol=1e-11)
@@ -87,6 +120,14 @@ def test_first_iterations_match_oracle_at_baseline_size(hip_abi, oracle_abi, whi
     assert np.allclose(h["lz_beta"][:K], o["lz_beta"][:K], rtol=1e-8, atol=1e-12 * scale)
     # … and what the dual bound actually uses, the smallest Ritz value of all q steps (src/coreop.jl:502-513)
     assert abs(h["ritz"] - o["ritz"]) <= 1e-6 * scale, (h["ritz"], o["ritz"])
+    # … and a bound that does not ask two decoupled runs to agree: every eigenvalue of the tridiagonal of a correct
+    # finite-precision run lies within τ = q·γ·‖|S|‖∞ of the spectrum of the S it ran on (the y dual_obj left), so the Ritz
+    # value the dual bound uses is no smaller than λ_min − τ.  λ_min: eigsh, whose value is a Ritz value itself (never below
+    # the true λ_min), converged to a residual below τ/10 (MaxCut: 2e-13 against τ = 1.7e-10).
+    lam_min, tau, resid = _lambda_min_and_tau(data, h["y_S"], h["q"])
+    print(f"{which}: Ritz {h['ritz']:.12g}, lambda_min {lam_min:.12g}, tau {tau:.3g}, eigsh residual {resid:.3g}")
+    assert resid <= 0.1 * tau, (resid, tau)
+    assert h["ritz"] >= lam_min - tau, (h["ritz"], lam_min, tau)
 
 
 def test_twenty_five_iterations_stay_within_the_north_star_tolerance(hip_abi, oracle_abi):
@@ -298,13 +339,16 @@ def test_lanczos_band_plan_at_full_bands_and_chunks(hip_abi, monkeypatch, n):
         g.inner_loop(normC, normb, True, True, False, 0.0, -1e300, 3, 0.0, *st)
         d, e = g.dual_obj(float(n), 0, v0)
         a, b, k = g.lanczos(60, v0)
-        out[form] = (d, e, a, b, k, g.tridiag_mineig(a, b))
+        out[form] = (d, e, a, b, k, g.tridiag_mineig(a, b), g.y)
         g.close()
-    (d1, e1, a1, b1, k1, m1), (d2, e2, a2, b2, k2, m2) = out["band"], out["gather"]
-    assert k1 == k2 == 60
+    (d1, e1, a1, b1, k1, m1, y1), (d2, e2, a2, b2, k2, m2, y2) = out["band"], out["gather"]
+    assert k1 == k2 == 60 and np.array_equal(y1, y2)        # the same S on both forms
     assert np.allclose(a1[:8], a2[:8], rtol=1e-9, atol=1e-12) and np.allclose(b1[:8], b2[:8], rtol=1e-9, atol=1e-12)
-    scale = max(1.0, float(np.max(np.abs(a2))))
-    assert abs(m1 - m2) <= 1e-6 * scale and abs(e1 - e2) <= 1e-6 * scale and d1 == pytest.approx(d2, rel=1e-6)
+    # two correct runs on the same S: smallest Ritz values within 2τ, τ = q·γ·‖|S|‖∞ (60 steps; dual_obj: 2⌈10·ln n⌉ steps)
+    q_dual = int(2 * np.ceil(10.0 * np.log(n)))
+    tau60, tau_dual = (_sparse_S_and_tau(data, y1, q)[2] for q in (60, q_dual))
+    print(f"n = {n}: Ritz difference {abs(m1 - m2):.3g} (2 tau {2 * tau60:.3g}), dual_obj's {abs(e1 - e2):.3g} (2 tau {2 * tau_dual:.3g})")
+    assert abs(m1 - m2) <= 2 * tau60 and abs(e1 - e2) <= 2 * tau_dual and d1 == pytest.approx(d2, rel=1e-6)
 
 
 def _omp_oracle():
