@@ -503,3 +503,484 @@ def break_instance(n: int = 150):
     y = np.concatenate([y, [1.0 / 16]])         # C = −¼L: S_34 = y_C·¼ = 1/64, C_jj = −¼
     S = S_dense_hp(C, As, y)
     return sj.SDPData(C, As, bs), y, S
+
+
+# ---- L-BFGS direction and exact line search above FP64 (tests/test_direction_linesearch_reference.py,
+# ---- tests/test_gpu_direction_linesearch.py) -------------------------------------------------------------------------------
+LD = np.longdouble
+
+
+def _ld(a):
+    return np.asarray(a, dtype=np.float64).astype(LD)
+
+
+def two_loop_hp(G, S_list, Y_list, latest: int, negate: bool = True) -> dict:
+    """The recursion of src/lbfgs.jl:77-124 as written — every dot taken on the running vector — in np.longdouble, on the
+    FP64 arrays read back from a handle (slot j of the handle = S_list[j], Y_list[j]; `latest` 1-based as the reference
+    keeps it).  ρ_j is recomputed as 1/⟨y_j, s_j⟩; a slot whose ⟨y_j, s_j⟩ is exactly 0 is an empty (cleared) one: ρ_j = 0
+    as lbfgs_clear! leaves it, so its α and γ vanish.  → dir, descent = ⟨dir, G⟩, alpha and gamma by slot, rho by slot, and
+    the termwise magnitude M = |G| + Σ|α_l||y_l| + Σ|γ_l||s_l| elementwise (what the final combination's terms add up to in
+    absolute value: any evaluation of dir rounds against it)."""
+    shape = np.shape(G)
+    g = _ld(G).ravel()
+    h = len(S_list)
+    d = g.copy()
+    M = np.abs(g)
+    al, ga, rho = np.zeros(h, dtype=LD), np.zeros(h, dtype=LD), np.zeros(h, dtype=LD)
+    if h == 0:              # :88-91: returns before the negation
+        return dict(dir=d.reshape(shape), descent=np.dot(d, g), alpha=al, gamma=ga, rho=rho, M=M.reshape(shape),
+                    run=dict(e=0.0, desc=float((g.size + 1) * LD(U53) * np.dot(np.abs(d), np.abs(g))), a=0.0))
+    S = [_ld(s).ravel() for s in S_list]
+    Y = [_ld(y).ravel() for y in Y_list]
+    # Running error bound of the LITERAL recursion in FP64, to first order and for ANY order of its sums (a dot of N terms
+    # within (N + 1)·u of Σ|terms|): E bounds |d_fp − d| elementwise, ea[j] |α_fp − α|.  Per stage: the dot inherits ⟨|v|, E⟩
+    # and adds its own (N + 1)u⟨|v|, |d| + E⟩; ρ_j = fl(1/fl⟨y, s⟩) is off by (N + 1)u·⟨|y|, |s|⟩/|⟨y, s⟩| + 2u relative; the
+    # coefficient's product rounds once; the axpy rounds its product and its sum.  Times 1.01 for the second-order terms.
+    u, N = LD(U53), g.size
+    gd = (N + 1) * u
+    E, ea, erho = np.zeros(N, dtype=LD), np.zeros(h, dtype=LD), np.zeros(h, dtype=LD)
+    for j in range(h):
+        ys = np.dot(Y[j], S[j])
+        rho[j] = 1 / ys if ys != 0 else LD(0)
+        erho[j] = gd * np.dot(np.abs(Y[j]), np.abs(S[j])) / abs(ys) + 2 * u if ys != 0 else LD(0)
+    j = int(latest) - 1
+    for _ in range(h):      # :93-102, newest → oldest
+        sd = np.dot(S[j], d)
+        e_sd = np.dot(np.abs(S[j]), E) + gd * np.dot(np.abs(S[j]), np.abs(d) + E)
+        al[j] = rho[j] * sd
+        ea[j] = LD(1.01) * (abs(rho[j]) * e_sd + (erho[j] + u) * abs(al[j]))
+        d = d - al[j] * Y[j]
+        E = LD(1.01) * (E + ea[j] * np.abs(Y[j]) + u * (np.abs(d) + 2 * abs(al[j]) * np.abs(Y[j])))
+        M = M + np.abs(al[j]) * np.abs(Y[j])
+        j = h - 1 if j <= 0 else j - 1
+    j = int(latest) % h
+    for _ in range(h):      # :104-113, oldest → newest
+        yd = np.dot(Y[j], d)
+        e_yd = np.dot(np.abs(Y[j]), E) + gd * np.dot(np.abs(Y[j]), np.abs(d) + E)
+        beta = rho[j] * yd
+        ga[j] = al[j] - beta
+        eg = LD(1.01) * (ea[j] + abs(rho[j]) * e_yd + (erho[j] + u) * abs(beta) + u * abs(ga[j]))
+        d = d + ga[j] * S[j]
+        E = LD(1.01) * (E + eg * np.abs(S[j]) + u * (np.abs(d) + 2 * abs(ga[j]) * np.abs(S[j])))
+        M = M + np.abs(ga[j]) * np.abs(S[j])
+        j = 0 if j == h - 1 else j + 1
+    if negate:
+        d = -d
+    run = dict(e=float(np.sqrt(np.sum(E * E)) / np.sqrt(np.sum(d * d))),
+               desc=float(np.dot(E, np.abs(g)) + gd * np.dot(np.abs(d) + E, np.abs(g))),
+               a=float(np.sqrt(np.sum(ea * ea)) / np.sqrt(np.sum(al * al))) if np.any(al != 0) else 0.0)
+    return dict(dir=d.reshape(shape), descent=np.dot(d, g), alpha=al, gamma=ga, rho=rho, M=M.reshape(shape), run=run)
+
+
+def direction_gamma(h: int, N: int) -> float:
+    """γ = (2h + 4 + ⌈log₂ N⌉)·u: 2h + 1 terms combined one after the other, each product rounded once, the coefficients'
+    own last rounding, and a pairwise dot of N terms where one follows."""
+    return (2 * h + 4 + int(np.ceil(np.log2(max(N, 2))))) * U53
+
+
+def direction_errors(hp: dict, dirt, descent, a=None) -> dict:
+    """e = ‖dir − dir_hp‖₂/‖dir_hp‖₂, |descent − descent_hp|, ‖a − α_hp‖₂/‖α_hp‖₂ of one evaluation against two_loop_hp."""
+    dd = _ld(dirt) - hp["dir"]
+    nrm = np.sqrt(np.sum(hp["dir"] ** 2))
+    out = dict(e=float(np.sqrt(np.sum(dd ** 2)) / nrm), desc=float(abs(LD(descent) - hp["descent"])))
+    if a is not None and len(hp["alpha"]):
+        na = np.sqrt(np.sum(hp["alpha"] ** 2))
+        out["a"] = float(np.sqrt(np.sum((_ld(a) - hp["alpha"]) ** 2)) / na) if na > 0 else 0.0
+    return out
+
+
+def direction_scales(hp: dict, G, S_list, h: int) -> dict:
+    """The termwise parts of the bounds of check 1: γ·max(M)/‖dir_hp‖∞ for dir, γ·Σ M|G| for descent,
+    γ·max_j |ρ_j|⟨|s_j|, M⟩/‖α_hp‖∞ for the coefficients (M dominates the running vector's terms at every stage)."""
+    N = int(np.size(G))
+    g = direction_gamma(h, N)
+    M = hp["M"].ravel()
+    out = dict(gamma=g, e=float(g * np.max(M) / np.max(np.abs(hp["dir"]))),
+               desc=float(g * np.sum(M * np.abs(_ld(G).ravel()))))
+    if h and np.max(np.abs(hp["alpha"])) > 0:
+        sc = max(abs(hp["rho"][j]) * np.dot(np.abs(_ld(S_list[j]).ravel()), M) for j in range(h))
+        out["a"] = float(g * sc / np.max(np.abs(hp["alpha"])))
+    else:
+        out["a"] = 0.0
+    return out
+
+
+def spd_quadratic(N: int, kappa: float, seed: int):
+    """H = Q·Diag(1 … κ, log-spaced)·Qᵀ in np.longdouble from a double Q (QR of a Gaussian matrix): symmetric positive
+    definite exactly, condition number κ up to the few ulp by which Q misses orthogonality; and a start point."""
+    rng = np.random.Generator(np.random.PCG64(9100 + seed))
+    Q, _ = np.linalg.qr(rng.standard_normal((N, N)))
+    ev = np.logspace(0.0, np.log10(kappa), N) if N > 1 else np.array([kappa])
+    Ql = Q.astype(LD)
+    H = (Ql * ev.astype(LD)) @ Ql.T
+    H = (H + H.T) / 2
+    return H, rng.standard_normal(N).astype(LD)
+
+
+def history_snapshot(s_, h: int) -> dict:
+    return dict(G=s_.Gt.copy(), S=[s_.get_factor(cabi.F_LBFGS_S + j).copy() for j in range(h)],
+                Y=[s_.get_factor(cabi.F_LBFGS_Y + j).copy() for j in range(h)],
+                rho=s_.get_vec(cabi.V_LBFGS_RHO).copy() if h else np.zeros(0),
+                latest=int(s_.get_scalar(cabi.S_LBFGS_LATEST)) if h else 0)
+
+
+def drive_quadratic_history(s_, h: int, kappa: float, seed: int, updates: int, repeat_at: int = -1) -> list:
+    """An L-BFGS history built through the ABI on the handle s_ (so it holds exactly the s, y, ρ a solve would leave): the
+    gradient field G(x) = fl(H·x) of spd_quadratic on N = n·r unknowns, Gt = G, lbfgs_dir(negate), the step α of the exact
+    line search −⟨d, Hx⟩/⟨d, Hd⟩ above FP64, x += α·d, Gt = G(x), lbfgs_update(α) — `updates` times, then one more
+    direction with negate = False.  repeat_at = k: at update k the direction is replaced from the host by the previous
+    one times (1 + 1e-9·ξ), ξ uniform in [−1, 1] — two consecutive pairs whose s differ by 1e-9 relative.
+    → one snapshot per direction: the state read back BEFORE the call (G, S, Y, rho, latest) and what the call returned
+    (dir, descent, a, negate).  The quadratic is homogeneous and, where N is not much larger than h, solved to round-off in
+    N steps and then again by sixteen orders of magnitude per cycle: 3h + 2 updates would leave the doubles.  So whenever
+    ‖G‖ has fallen below 1e-10·‖G₀‖ — far inside the regime ‖q‖ ≪ ‖G‖ the histories are for — the quadratic's centre jumps to
+    a fresh Gaussian point of the start point's size, G(x) = fl(H·(x − c)): the pair formed across the jump is one of a
+    function that is not quadratic, all others satisfy y = H·s to round-off."""
+    n, r = s_.n, s_.r
+    H, x = spd_quadratic(n * r, kappa, seed)
+    rng = np.random.Generator(np.random.PCG64(77 + seed))
+    s_.lbfgs_clear()
+    snaps, prev = [], None
+    c, x0n = np.zeros(n * r, dtype=LD), np.sqrt(np.sum(x * x))
+    G = np.asarray(H @ x, dtype=np.float64).reshape(n, r)
+    g0 = float(np.linalg.norm(G))
+    for k in range(updates + 1):
+        s_.Gt = G
+        snap = history_snapshot(s_, h)
+        negate = k < updates
+        snap["descent"] = s_.lbfgs_dir(negate)
+        snap["dir"], snap["negate"] = s_.dirt.copy(), negate
+        snap["a"] = s_.get_vec(cabi.V_LBFGS_A).copy() if h else np.zeros(0)
+        snaps.append(snap)
+        if not negate:
+            break
+        d64 = snap["dir"]
+        if k == repeat_at and prev is not None:
+            d64 = prev * (1.0 + 1e-9 * rng.uniform(-1.0, 1.0, size=prev.shape))
+            s_.dirt = d64
+        d = d64.astype(LD).ravel()
+        alpha = float(-np.dot(d, H @ (x - c)) / np.dot(d, H @ d))
+        if k == repeat_at and prev is not None:
+            alpha = snaps[-2]["step"]        # the same step length again: s repeats to 1e-9, not just its direction
+        x = x + LD(alpha) * d
+        G = np.asarray(H @ (x - c), dtype=np.float64).reshape(n, r)
+        if float(np.linalg.norm(G)) < 1e-10 * g0:
+            snap["jump"] = True
+            c = c + x0n * rng.standard_normal(n * r).astype(LD) / np.sqrt(LD(n * r))
+            G = np.asarray(H @ (x - c), dtype=np.float64).reshape(n, r)
+        s_.Gt = G
+        s_.lbfgs_update(alpha)
+        prev = d64.copy()                # the direction s was formed from
+        snap["step"] = alpha
+    return snaps
+
+
+def load_history(o, snap: dict, h: int):
+    """A snapshot's state into another handle of the same (n, r, h): the slots, ρ, latest and G."""
+    for j in range(h):
+        o.set_factor(cabi.F_LBFGS_S + j, snap["S"][j])
+        o.set_factor(cabi.F_LBFGS_Y + j, snap["Y"][j])
+    if h:
+        o.set_vec(cabi.V_LBFGS_RHO, snap["rho"])
+        o.set_scalar(cabi.S_LBFGS_LATEST, float(snap["latest"]))
+    o.Gt = snap["G"]
+
+
+def check_direction_snapshots(snaps: list, h: int, oracle_solver, literal: bool = False) -> dict:
+    """Check 1 on every snapshot: the literal FP64 evaluation (the oracle, on the same state) gives e_lit; the evaluation
+    under test must meet e ≤ 8·e_lit + γ·max(M)/‖dir_hp‖∞, and the same for descent (scale ΣM|G|) and the coefficients.
+    literal = True (the evaluation under test IS the literal recursion, in another summation order): e_lit is then ONE sample
+    of the same error distribution, and on few unknowns the ratio of two such samples exceeds 8 every dozen draws (for two
+    half-normal magnitudes P(ratio > 8) = (2/π)·atan(1/8) ≈ 8 %); such an evaluation is held to the larger of the bound above
+    and the running bound of two_loop_hp, which every correct literal evaluation meets whatever its order.
+    → per quantity the largest error/bound with its step, the largest e/e_lit, the literal evaluation's own largest
+    error/running bound (≤ 1 shows the running bound attainable), the number of centre jumps, and the failures as text."""
+    worst = dict(ratio_lit=0.0, dir=0.0, desc=0.0, a=0.0, lit_dir=0.0, lit_run=0.0, run=0.0)
+    bad = []
+    for k, sn in enumerate(snaps):
+        hp = two_loop_hp(sn["G"], sn["S"], sn["Y"], sn["latest"], sn["negate"])
+        load_history(oracle_solver, sn, h)
+        dl = oracle_solver.lbfgs_dir(sn["negate"])
+        lit = direction_errors(hp, oracle_solver.dirt, dl, oracle_solver.get_vec(cabi.V_LBFGS_A) if h else None)
+        err = direction_errors(hp, sn["dir"], sn["descent"], sn["a"] if h else None)
+        sc = direction_scales(hp, sn["G"], sn["S"], h)
+        worst["lit_dir"] = max(worst["lit_dir"], lit["e"] / sc["e"])
+        if lit["e"] > 0:
+            worst["ratio_lit"] = max(worst["ratio_lit"], err["e"] / lit["e"])
+        for key, name in (("e", "dir"), ("desc", "desc"), ("a", "a")):
+            if key not in err:
+                continue
+            if hp["run"][key] > 0:
+                worst["lit_run"] = max(worst["lit_run"], lit[key] / hp["run"][key])
+                worst["run"] = max(worst["run"], err[key] / hp["run"][key])
+            bound = 8 * lit[key] + sc[key]
+            if literal:
+                bound = max(bound, hp["run"][key])
+            ratio = err[key] / bound if bound > 0 else (0.0 if err[key] == 0 else np.inf)
+            worst[name] = max(worst[name], ratio)
+            if not ratio <= 1.0:
+                bad.append(f"step {k} {name}: err {err[key]:.3g} lit {lit[key]:.3g} termwise {sc[key]:.3g} ratio {ratio:.3g}")
+    return dict(worst=worst, bad=bad, jumps=sum(1 for sn in snaps if sn.get("jump")))
+
+
+# -- the exact line search ---------------------------------------------------------------------------------------------------
+def _mat_hp(M) -> np.ndarray:
+    if isinstance(M, sj.SymLowRankMatrix):
+        B = M.B.astype(LD)
+        return (B * M.D.astype(LD)) @ B.T
+    if hasattr(M, "is_"):           # SparseMatrixCOO: its entries, duplicates added
+        out = np.zeros((M.n, M.n) if hasattr(M, "n") else M.shape, dtype=LD)
+        np.add.at(out, (np.asarray(M.is_), np.asarray(M.js)), np.asarray(M.vs, dtype=np.float64).astype(LD))
+        return out
+    return np.asarray(dense(M), dtype=np.float64).astype(LD)
+
+
+def loop_state_direction(sn: dict, h: int, oracle_solver) -> dict:
+    """The direction of the iteration that follows a loop's state (history_snapshot of a handle after k iterations): above
+    FP64, with the literal FP64 evaluation (the oracle's lbfgs_dir on the same state) as e_lit, the termwise scales, and
+    whether the sign of descent_hp is decided: |descent_hp| > 8·|descent_lit − descent_hp| + γ·ΣM|G| (check 3)."""
+    hp = two_loop_hp(sn["G"], sn["S"], sn["Y"], sn["latest"], True)
+    load_history(oracle_solver, sn, h)
+    dl = oracle_solver.lbfgs_dir(True)
+    lit = direction_errors(hp, oracle_solver.dirt, dl)
+    sc = direction_scales(hp, sn["G"], sn["S"], h)
+    return dict(hp=hp, lit=lit, sc=sc, decided=bool(abs(float(hp["descent"])) > 8 * lit["desc"] + sc["desc"]))
+
+
+def quartic_hp(C, As, bs, R, D, lam, pv_raw, obj, sigma) -> dict:
+    """src/linesearch.jl:8-56 in np.longdouble from dense matrices: A_RD = 𝒜(RDᵀ + DRᵀ) (with its ×2, :13), A_DD = 𝒜(DDᵀ)
+    (both of length m + 1, the cost matrix last), the quartic's coefficients b_0 … b_4 (:44-56) with p0 = obj and −q0 =
+    pv_raw[:m] as given — and for each output the sum of the magnitudes of its terms (A_RD_mag, A_DD_mag, b_mag): the
+    scale any FP64 evaluation of it rounds against.  bs is not read (pv_raw carries it); kept for the call's symmetry."""
+    Rl, Dl = _ld(R), _ld(D)
+    X, XX = Rl @ Dl.T, Dl @ Dl.T
+    X = X + X.T
+    aX = np.abs(Rl) @ np.abs(Dl).T
+    aX, aXX = aX + aX.T, np.abs(Dl) @ np.abs(Dl).T
+    mats = list(As) + [C]
+    m = len(As)
+    q1, q2, q1m, q2m = (np.zeros(m + 1, dtype=LD) for _ in range(4))
+    for i, A in enumerate(mats):
+        Al = _mat_hp(A)
+        q1[i], q2[i] = np.sum(Al * X), np.sum(Al * XX)
+        q1m[i], q2m[i] = np.sum(np.abs(Al) * aX), np.sum(np.abs(Al) * aXX)
+    lam_, nq0, sg, p0 = _ld(lam), _ld(pv_raw)[:m], LD(sigma), LD(obj)
+    a1, a2, m1, m2 = q1[:m], q2[:m], q1m[:m], q2m[:m]
+    al, an = np.abs(lam_), np.abs(nq0)
+    b = np.array([p0 - np.dot(lam_, nq0) + sg * np.dot(nq0, nq0) / 2,
+                  q1[m] - np.dot(lam_, a1) + sg * np.dot(nq0, a1),
+                  q2[m] - np.dot(lam_ - sg * nq0, a2) + sg * np.dot(a1, a1) / 2,
+                  sg * np.dot(a1, a2),
+                  sg * np.dot(a2, a2) / 2], dtype=LD)
+    bm = np.array([abs(p0) + np.dot(al, an) + sg * np.dot(an, an) / 2,
+                   q1m[m] + np.dot(al, m1) + sg * np.dot(an, m1),
+                   q2m[m] + np.dot(al + sg * an, m2) + sg * np.dot(m1, m1) / 2,
+                   sg * np.dot(m1, m2),
+                   sg * np.dot(m2, m2) / 2], dtype=LD)
+    return dict(A_RD=q1, A_DD=q2, A_RD_mag=q1m, A_DD_mag=q2m, b=b, b_mag=bm)
+
+
+def poly_hp(b, a):
+    a = LD(a)
+    v = LD(0)
+    for c in b[::-1]:
+        v = v * a + LD(c)
+    return v
+
+
+def poly_T(b, a) -> float:
+    """T(α) = Σ|b_k|·α^k."""
+    return float(poly_hp(np.abs(np.asarray(b, dtype=LD)), abs(a)))
+
+
+def quartic_min_hp(b, alpha_max) -> dict:
+    """The global minimum of b_0 + … + b_4·α⁴ over [0, α_max] in np.longdouble: the stationary points from np.roots on the
+    derivative (real parts of all of them — a pair that rounding made complex still marks where the derivative nearly
+    vanishes), polished by Newton in long double and kept where they stay inside, both end points, and — as a guard against
+    a stationary point np.roots misplaced — the best point of a 4001-point grid refined by ternary search; the smallest
+    value wins.  → alpha, fmin, and T = poly_T(b, ·)."""
+    b = np.asarray(b, dtype=LD)
+    amax = LD(alpha_max)
+    db = np.array([k * b[k] for k in range(1, 5)], dtype=LD)
+    ddb = np.array([k * db[k] for k in range(1, 4)], dtype=LD)
+    cands = [LD(0), amax]
+    d64 = np.asarray(db, dtype=np.float64)
+    if np.all(np.isfinite(d64)) and np.any(d64 != 0):
+        for z in np.roots(d64[::-1]):
+            x = LD(z.real)
+            for _ in range(8):
+                fp, fpp = poly_hp(db, x), poly_hp(ddb, x)
+                if fpp == 0 or not np.isfinite(fp / fpp):
+                    break
+                x = x - fp / fpp
+            for c in (LD(z.real), x):
+                if np.isfinite(c) and 0 <= c <= amax:
+                    cands.append(c)
+    grid = amax * np.arange(4001, dtype=LD) / 4000
+    vals = b[0] + grid * (b[1] + grid * (b[2] + grid * (b[3] + grid * b[4])))
+    k = int(np.argmin(vals))
+    lo, hi = grid[max(k - 1, 0)], grid[min(k + 1, 4000)]
+    for _ in range(200):
+        m1, m2 = lo + (hi - lo) / 3, hi - (hi - lo) / 3
+        if poly_hp(b, m1) <= poly_hp(b, m2):
+            hi = m2
+        else:
+            lo = m1
+    cands.append((lo + hi) / 2)
+    fv = [poly_hp(b, c) for c in cands]
+    i = int(np.argmin(fv))
+    return dict(alpha=cands[i], fmin=fv[i], T=lambda a: poly_T(b, a))
+
+
+LS_T = (1.0, 1e-2, 1e-4, 1e-6)
+LS_AMAX = (1e-3, 0.5, 1.0, 4.0)
+LS_RECIPES = ("three_roots", "near_double", "beyond", "zero_plus")
+LS_SIGMA = 2.0
+_LS_CACHE = {}
+
+
+def linesearch_base(family: str, r: int) -> dict:
+    """(seed, n, p) = (2, 12, 0.4) of `family` with a seeded Gaussian R (n×r), σ = 2, a seeded λ₀, the violation
+    𝒜(RRᵀ) − b and objective at R, and G = ∇ℒ(R; λ₀) above FP64 (hp_gradient) rounded to double."""
+    key = (family, r)
+    if key not in _LS_CACHE:
+        data, C, As, bs = make_data(family, 2, 12, 0.4)
+        rng = np.random.Generator(np.random.PCG64(5200 + 7 * r + sorted(FAMILIES_EQ).index(family)))
+        R = rng.standard_normal((data.n, r))
+        lam0 = rng.standard_normal(data.m)
+        Rl = R.astype(LD)
+        XX = Rl @ Rl.T
+        pv = np.array([np.sum(_mat_hp(A) * XX) for A in As] + [np.sum(_mat_hp(C) * XX)], dtype=LD)
+        pv[:data.m] -= _ld(bs)
+        G = np.asarray(hp_gradient(C, As, bs, R, lam0, LS_SIGMA), dtype=np.float64)
+        _LS_CACHE[key] = dict(family=family, r=r, data=data, C=C, As=As, bs=bs, R=R, G=G, pv_raw=np.asarray(pv, dtype=np.float64),
+                              nnz=[int(np.count_nonzero(np.asarray(_mat_hp(A), dtype=np.float64))) for A in list(As) + [C]])
+    return _LS_CACHE[key]
+
+
+def linesearch_state(base: dict, t: float, amax: float, recipe: str):
+    """One line-search state: D = fl(t·D₀), D₀ = ±c·G with sign and c such that the derivative's roots sum to 0.9·α_max at
+    t = 1 (the sum is −3b₃/4b₄ = −3⟨q1, q2⟩/2‖q2‖², a property of R and D alone), and λ chosen above FP64 so that b₁ and b₂
+    — the two coefficients λ moves — give the derivative 4b₄·Π(α − ρ_i) the roots of the recipe (the third root or the real
+    part of a complex pair follows from the fixed sum):
+      three_roots   ρ = Σ·(1/6, 1/3, 1/2), all inside (0, α_max): needs Σ/2 < α_max, i.e. t = 1
+      near_double   ρ, ρ·(1 + 1e-9) with ρ = 0.3·α_max, the third root Σ − ρ₁ − ρ₂ > 0
+      beyond        one real root 2·α_max and a complex pair: the derivative is negative on [0, α_max]
+      zero_plus     one real root 1e-9·α_max and a complex pair: the minimiser is at 0⁺
+    λ = x₁q1 + x₂q2 on all but two components, rounded, then the two left out absorb what the rounding moved (they are of
+    the size of that residual, so their own rounding is ≈ 2⁻¹⁰⁶ relative).  pv_raw and obj are the true ones at R.
+    The structure is claimed (claimed = True, asserted above FP64 in tests/test_direction_linesearch_reference.py) at
+    t ≥ 1e-2 only.  b₁ … b₄ scale as t¹ … t⁴, so roots of the size of α_max ask b₁ to cancel to ≈ t²·α_max² of its terms; from
+    t = 1e-4 on that is below what FP64 — and soon long double — resolves of the state, and the recipe is only where λ was
+    aimed.  What those states pin is the scaling b_k ∝ |D|^k, the quadratic branch |4b₄| < eps (:70), and a λ whose b₁ and
+    b₂ are differences of much larger terms: A_RD, A_DD, ℒ, the optimality gap and the commit are checked on them as on
+    every state, against the quartic the state really has.
+    → None where the recipe cannot be met (three_roots at t < 1), else the arrays to set and the targets."""
+    C, As, bs, R, G, pv_raw = (base[k] for k in ("C", "As", "bs", "R", "G", "pv_raw"))
+    m = len(As)
+    sg = LD(LS_SIGMA)
+    z = np.zeros(m)
+    q = quartic_hp(C, As, bs, R, -G, z, pv_raw, pv_raw[m], LS_SIGMA)
+    sum_unit = -3 * q["b"][3] / (4 * q["b"][4])
+    c = float(abs(sum_unit) / (LD(0.9) * LD(amax)))
+    D = np.asarray(t * (np.sign(float(sum_unit)) * c * (-G)), dtype=np.float64)
+    q = quartic_hp(C, As, bs, R, D, z, pv_raw, pv_raw[m], LS_SIGMA)
+    b3, b4 = q["b"][3], q["b"][4]
+    Sm = -3 * b3 / (4 * b4)
+    am = LD(amax)
+    if recipe == "three_roots":
+        if not Sm / 2 < am:
+            return None
+        roots = (Sm / 6, Sm / 3, Sm / 2)
+        e2, e3 = roots[0] * roots[1] + roots[0] * roots[2] + roots[1] * roots[2], roots[0] * roots[1] * roots[2]
+    elif recipe == "near_double":
+        r1 = LD(0.3) * am
+        r2 = r1 * (1 + LD(1e-9))
+        r3 = Sm - r1 - r2
+        if not r3 > 0:
+            return None
+        roots = (r1, r2, r3)
+        e2, e3 = r1 * r2 + r1 * r3 + r2 * r3, r1 * r2 * r3
+    else:
+        r1 = 2 * am if recipe == "beyond" else LD(1e-9) * am
+        a = (Sm - r1) / 2
+        bb = am + abs(a)
+        roots = (r1,)
+        e2, e3 = 2 * a * r1 + a * a + bb * bb, r1 * (a * a + bb * bb)
+    b1t, b2t = -4 * b4 * e3, 2 * b4 * e2
+    q1, q2, nq0 = q["A_RD"][:m], q["A_DD"][:m], _ld(pv_raw)[:m]
+    L1 = q["A_RD"][m] + sg * np.dot(nq0, q1) - b1t
+    L2 = q["A_DD"][m] + sg * np.dot(nq0, q2) + sg * np.dot(q1, q1) / 2 - b2t
+    dets = np.abs(np.outer(q1, q2) - np.outer(q2, q1)) / (np.outer(np.abs(q1), np.abs(q2)) + np.outer(np.abs(q2), np.abs(q1)) + LD(1e-300))
+    i, j = np.unravel_index(int(np.argmax(dets)), dets.shape)
+    keep = np.ones(m, dtype=bool)
+    keep[[i, j]] = False
+    u1, u2 = q1 * keep, q2 * keep
+    g11, g12, g22 = np.dot(u1, u1), np.dot(u1, u2), np.dot(u2, u2)
+    det = g11 * g22 - g12 * g12
+    x1, x2 = (L1 * g22 - L2 * g12) / det, (L2 * g11 - L1 * g12) / det
+    lam = np.asarray(x1 * u1 + x2 * u2, dtype=np.float64)
+    ll = _ld(lam)
+    r1_, r2_ = L1 - np.dot(ll, q1), L2 - np.dot(ll, q2)
+    d2 = q1[i] * q2[j] - q1[j] * q2[i]
+    lam[i], lam[j] = float((r1_ * q2[j] - r2_ * q1[j]) / d2), float((r2_ * q1[i] - r1_ * q2[i]) / d2)
+    return dict(R=R, D=D, lam=lam, pv_raw=pv_raw.copy(), obj=float(pv_raw[m]), sigma=LS_SIGMA, t=t, amax=amax, recipe=recipe,
+                claimed=bool(t >= 1e-2), b4x4=float(4 * b4),
+                roots=roots, sum=Sm, quad_branch=bool(abs(float(4 * b4)) < np.finfo(np.float64).eps))
+
+
+def apply_linesearch_state(s_, st: dict):
+    s_.Rt, s_.dirt = st["R"], st["D"]
+    s_.λ = st["lam"]
+    s_.primal_vio_raw = st["pv_raw"]
+    s_.obj, s_.σ = st["obj"], st["sigma"]
+
+
+def linesearch_c(m: int) -> float:
+    """c = 2·(⌈log₂ m⌉ + 12): the eight or ten sums over m constraints taken pairwise, and a dozen roundings in the
+    coefficients and Horner's rule — times two."""
+    return 2.0 * (int(np.ceil(np.log2(max(m, 2)))) + 12)
+
+
+def check_linesearch_call(base: dict, st: dict, solver) -> dict:
+    """Check 4 on one state and one handle (state applied, linesearch(α_max) run here).  → error/bound ratios
+    (A_RD, A_DD, L, opt, commit) and the exact properties as booleans; nothing is asserted here."""
+    C, As, bs = base["C"], base["As"], base["bs"]
+    m, r = len(As), base["r"]
+    apply_linesearch_state(solver, st)
+    alpha, L = solver.linesearch(st["amax"])
+    q = quartic_hp(C, As, bs, st["R"], st["D"], st["lam"], st["pv_raw"], st["obj"], st["sigma"])
+    out = {}
+    # d = 3: a term A_jk·R_jc·D_kc of ⟨A, RDᵀ + DRᵀ⟩ is two products, and the ×2 of :13 (or the sum of the two halves) a third
+    depth = np.array([3 + int(np.ceil(np.log2(k + r))) + 4 for k in base["nnz"]]) * U53
+    for name, got in (("A_RD", solver.A_RD), ("A_DD", solver.A_DD)):
+        err = np.abs(_ld(got) - q[name])
+        bound = depth * q[name + "_mag"]
+        ok = bound > 0
+        assert np.all(err[~ok] == 0), name
+        out[name] = float(np.max(err[ok] / bound[ok])) if ok.any() else 0.0
+    mn = quartic_min_hp(q["b"], st["amax"])
+    cc = linesearch_c(m)
+    f_at = poly_hp(q["b"], alpha)
+    out["L"] = float(abs(LD(L) - f_at) / (cc * U53 * mn["T"](alpha)))
+    out["opt"] = float((f_at - mn["fmin"]) / (2 * cc * U53 * mn["T"](st["amax"])))
+    out["inside"] = bool(0.0 <= alpha <= st["amax"])
+    out["alpha"], out["alpha_hp"] = alpha, float(mn["alpha"])
+    # the commit (:118-124) is a kernel of its own that reads the A_RD and A_DD the call left: pv_raw + α(α·A_DD + A_RD) of
+    # THOSE vectors (themselves held to quartic_hp above) in long double, to 4 ulp of its term magnitudes; V_PV is its
+    # max with the lower bounds and S_OBJ its last entry, to the same
+    a = LD(alpha)
+    ard, add = _ld(solver.A_RD), _ld(solver.A_DD)
+    want = _ld(st["pv_raw"]) + a * (a * add + ard)
+    tol = 4 * U53 * (np.abs(_ld(st["pv_raw"])) + a * (a * np.abs(add) + np.abs(ard)))
+    pv = solver.primal_vio_raw
+    lb = _ld(solver.primal_vio_lb)
+    errs = np.concatenate([np.abs(_ld(pv) - want), np.abs(_ld(solver.primal_vio) - np.maximum(want[:m], lb)),
+                           [abs(LD(solver.obj) - want[m])]])
+    tols = np.concatenate([tol, tol[:m], [tol[m]]])
+    ok = tols > 0
+    assert np.all(errs[~ok] == 0)
+    out["commit"] = float(np.max(errs[ok] / tols[ok]))
+    out["obj_is_last"] = bool(solver.obj == pv[m])
+    out["pv_is_raw"] = bool(np.array_equal(solver.primal_vio, np.maximum(pv[:m], solver.primal_vio_lb)))
+    return out

@@ -9,8 +9,8 @@ import scipy.sparse as sp
 
 import sdplrplus_jl_amd as sj
 from sdplrplus_jl_amd import cabi, problems
-from helpers import (FAMILIES_EQ, GRID, S_dense, lagrangian_dense, lanczos_tau, make_data, make_solver,
-                     primal_vio_dense)
+from helpers import (FAMILIES_EQ, GRID, S_dense, U53, lagrangian_dense, lanczos_tau, linesearch_c, make_data, make_solver,
+                     poly_hp, primal_vio_dense, quartic_hp, quartic_min_hp)
 
 pytestmark = pytest.mark.gpu
 
@@ -70,8 +70,15 @@ def test_operators_match_oracle_and_dense(hip_abi, oracle_abi, family, seed, n, 
         (ag, Lg2), (ao, Lo2) = g.linesearch_armijo(1.0), o.linesearch_armijo(1.0)
         assert ag == ao
     else:
+        pv0, obj0, lam0 = g.primal_vio_raw, g.obj, g.λ
         (ag, Lg2), (ao, Lo2) = g.linesearch(1.0), o.linesearch(1.0)
         assert abs(ag - ao) <= 1e-7 * max(1.0, abs(ao))
+        # α moves freely on a flat minimum and 1e-7 would pass the wrong one of three close stationary points: the value
+        # at the returned α against the quartic's minimum over [0, 1] above FP64 (tests/test_gpu_direction_linesearch.py)
+        qh = quartic_hp(C, As, bs, R, -G, lam0, pv0, obj0, 2.0)
+        mn = quartic_min_hp(qh["b"], 1.0)
+        assert 0.0 <= ag <= 1.0
+        assert float(poly_hp(qh["b"], ag) - mn["fmin"]) <= 2 * linesearch_c(data.m) * U53 * mn["T"](1.0)
     assert abs(Lg2 - Lo2) <= 1e-10 * max(1, abs(Lo2))
     assert rel(g.A_RD, o.A_RD) < 1e-12 and rel(g.A_DD, o.A_DD) < 1e-12
     g.axpy_R(ag)
