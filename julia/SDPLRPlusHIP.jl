@@ -325,6 +325,47 @@ function DIMACS_errors(data, var::SolverVars, aux::HIPAux)
     return [err1, 0.0, 0.0, err4, err5, err6]
 end
 
+# ---- randomized rounding on the device (include/sdplr_hip_round.h) -----------------------------------------------
+# The callbacks of the reference's runner (exps/test.jl:71-105, called at :132 as callback(A, R)) on the factor where it
+# lies.  Like the rest of this file these methods could not be executed in the build image (no Julia there).  The two
+# entry points are an extension declared in a header of their own; their ccalls go through LIBSDPLR_HIP_ROUND (the same
+# library) and are checked against THAT header by tests/test_round_julia_binding.py.
+const LIBSDPLR_HIP_ROUND = LIBSDPLR_HIP
+
+"uploads the graph the cuts are scored on: the entries i < j of A (1-based, as findnz returns them)"
+function hip_round_set_graph!(aux::HIPAux, A::SparseMatrixCSC{Float64})
+    I, J, V = findnz(A)
+    hip_check(ccall((:sdplr_hip_round_set_graph, LIBSDPLR_HIP_ROUND), Int32,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                    aux.handle, 1, length(I), Vector{Int64}(I), Vector{Int64}(J), Vector{Float64}(V)), aux.handle)
+    return nothing
+end
+
+"`trials` roundings of the device's R in one call → (cuts, index of the best trial, 1-based); Γ is r×trials, drawn here"
+function hip_round(aux::HIPAux, mode::Integer, r::Integer, trials::Integer)
+    Γ = randn(r, trials)                       # one column per trial, as exps/test.jl:77,91 draw them
+    cuts = zeros(trials)
+    best = Ref{Int64}(0)
+    hip_check(ccall((:sdplr_hip_round, LIBSDPLR_HIP_ROUND), Int32,
+                    (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int8}, Ptr{Int8}),
+                    aux.handle, mode, HIP_F_RT, trials, Γ, cuts, best, C_NULL, C_NULL), aux.handle)
+    return cuts, Int(best[]) + 1
+end
+
+"maxcut_rounding(A, R) — exps/test.jl:71-81, on the R the device holds (r = its current rank)"
+function maxcut_rounding(A::SparseMatrixCSC{Float64}, aux::HIPAux, r::Integer; trials::Integer=100)
+    hip_round_set_graph!(aux, A)
+    cuts, best = hip_round(aux, 0, r, trials)
+    return cuts[best]
+end
+
+"minimumbisection_rounding(A, R) — exps/test.jl:83-98, on the R the device holds"
+function minimumbisection_rounding(A::SparseMatrixCSC{Float64}, aux::HIPAux, r::Integer; trials::Integer=100)
+    hip_round_set_graph!(aux, A)
+    cuts, best = hip_round(aux, 1, r, trials)
+    return cuts[best]
+end
+
 # ---- the solve loop -------------------------------------------------------------------------------------------
 """
     _sdplr(data, var, aux::HIPAux, stats, config)

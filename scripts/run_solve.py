@@ -26,7 +26,10 @@ def load_graph(name):
     return problems.graph_from_edges(int(z[f"{name}_n"]), z[name])
 
 
-from sdplrplus_jl_amd.rounding import maxcut_rounding, minimumbisection_rounding  # noqa: E402  (exps/test.jl:67-105)
+from sdplrplus_jl_amd.rounding import (maxcut_rounding, maxcut_rounding_device, minimumbisection_rounding,  # noqa: E402
+                                       minimumbisection_rounding_device)                       # (exps/test.jl:67-105)
+
+DEVICE_ROUNDING = {maxcut_rounding: maxcut_rounding_device, minimumbisection_rounding: minimumbisection_rounding_device}
 
 
 PROBLEMS = {  # name → (builder, rounding callback, trace bound as a function of n)   exps/test.jl:166-176
@@ -37,14 +40,21 @@ PROBLEMS = {  # name → (builder, rounding callback, trace bound as a function 
 }
 
 
-def batch_eval(problem, graph, A, r, seed, out_dir, tag, **kw):
+def batch_eval(problem, graph, A, r, seed, out_dir, tag, rounding="host", **kw):
     builder, callback, tb = PROBLEMS[problem]
     data = builder(A)
-    res = sj.sdplr(data=data, r=r, prior_trace_bound=float(tb(data.n)), dataset=graph, seed=seed, **kw)
     rng = np.random.Generator(np.random.PCG64(seed + 1))
-    res["callback_res"] = callback(A, res["Rt"], rng) if callback else 0
+    hook = None
+    if callback is not None:       # the reference's callback slot (exps/test.jl:132): on the live handle, before it closes
+        if rounding == "device":
+            hook = lambda var, _data: DEVICE_ROUNDING[callback](var, A, rng)
+        else:
+            hook = lambda var, _data: callback(A, var.Rt, rng)
+    res = sj.sdplr(data=data, r=r, prior_trace_bound=float(tb(data.n)), dataset=graph, seed=seed, callback=hook, **kw)
+    res.setdefault("callback_res", 0)
+    res.setdefault("callback_time", 0.0)
     keys = ["grad_norm", "primal_vio", "obj", "max_dual_value", "min_duality_gap", "totaltime", "dual_time",
-            "primaltime", "iter", "majoriter", "ptol", "objtol", "fprec", "callback_res", "rankupd_tol", "r"]
+            "primaltime", "iter", "majoriter", "ptol", "objtol", "fprec", "callback_res", "callback_time", "rankupd_tol", "r"]
     short = {k: (float(res[k]) if isinstance(res[k], (np.floating, float)) else res[k]) for k in keys}
     if out_dir:
         path = os.path.join(out_dir, problem, graph)
@@ -64,6 +74,8 @@ def main():
     ap.add_argument("--problem", default="MaxCut", choices=list(PROBLEMS))
     ap.add_argument("--output", default=None, help="folder for the JSON result (exps/test.jl writes exps/output/)")
     ap.add_argument("--printlevel", type=int, default=0)
+    ap.add_argument("--rounding", default="host", choices=["host", "device"],
+                    help="where the rounding callback runs: host numpy on the downloaded factor, or the device kernels")
     args = ap.parse_args()
     A1 = load_graph("G1")
     batch_eval(args.problem, "G1", A1, args.rank, args.seed, None, "SDPLR-warmup", maxtime=36000.0, objtol=1.0,
@@ -71,7 +83,7 @@ def main():
     A = load_graph(args.graph)
     short = batch_eval(args.problem, args.graph, A, args.rank, args.seed, args.output,
                        f"SDPLR-R-{args.rank}-seed-{args.seed}-tol-{args.ptol}", maxtime=36000.0,
-                       objtol=args.objtol, ptol=args.ptol, printlevel=args.printlevel)   # :198-210
+                       objtol=args.objtol, ptol=args.ptol, printlevel=args.printlevel, rounding=args.rounding)   # :198-210
     print(json.dumps(short))
 
 

@@ -119,6 +119,15 @@ SIGNATURES = {
     "profile_get": [_vp, _i32, C.c_char_p, _i32, _pi64, _pf64],
 }
 _RESTYPES = {"last_error": C.c_char_p, "version": C.c_char_p}
+_pi8 = C.POINTER(C.c_int8)
+# include/sdplr_hip_round.h (randomized rounding on the device), checked against that header by tests/test_round_cabi.py.
+# An extension: bound only when the library exports it (the CPU checker's ABI does not).
+ROUND_SIGNATURES = {
+    "round_set_graph": [_vp, _i64, _i64, _pi64, _pi64, _pf64],
+    "round": [_vp, _i32, _i32, _i64, _pf64, _pf64, _pi64, _pi8, _pi8],
+}
+ROUND_HYPERPLANE, ROUND_BISECTION = 0, 1
+ROUND_MAX_TRIALS = 4096
 
 
 class SdplrError(RuntimeError):
@@ -143,6 +152,13 @@ class CABI:
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, _i32)
             setattr(self, name, fn)
+        self.has_round = all(hasattr(self.lib, prefix + name) for name in ROUND_SIGNATURES)
+        if self.has_round:
+            for name, argtypes in ROUND_SIGNATURES.items():
+                fn = getattr(self.lib, prefix + name)
+                fn.argtypes = argtypes
+                fn.restype = _i32
+                setattr(self, name, fn)
 
     def version_string(self) -> str:
         return self.version().decode()
@@ -510,6 +526,44 @@ class DeviceSolver:
         self._ck(self.abi.dual_obj(self._h, float(trace_bound), int(iter_), _pd(v0), C.byref(d),
                                    C.byref(e)))
         return float(d.value), float(e.value)
+
+    # -- randomized rounding on the device (include/sdplr_hip_round.h) ----------------------------------
+    def _need_round(self):
+        if not getattr(self.abi, "has_round", False):
+            raise NotImplementedError(f"{self.abi.path} does not export the rounding entry points")
+
+    def round_set_graph(self, A):
+        """The graph the cuts are scored on: a scipy sparse adjacency matrix (both triangles or the upper one), or a
+        triple (I, J, W) of 0-based COO arrays.  Replaces an earlier graph; survives reset_rank."""
+        self._need_round()
+        if isinstance(A, tuple):
+            I, J, W = A
+        else:
+            import scipy.sparse as sp
+            co = sp.coo_matrix(A)
+            I, J, W = co.row, co.col, co.data
+        I, J, W = _i64c(I), _i64c(J), _f64c(W)
+        if not (I.size == J.size == W.size):
+            raise ValueError("I, J, W must have the same length")
+        self._ck(self.abi.round_set_graph(self._h, 0, int(I.size), _pl(I), _pl(J), _pd(W)))
+
+    def round(self, mode: int, trials: int, gauss, slot: int = F_RT, want_best: bool = False, want_labels: bool = False):
+        """``trials`` random roundings of factor slot ``slot`` on the device (exps/test.jl:71-105): mode 0 hyperplane, mode 1
+        bisection.  gauss: (trials, r), row t the Gaussian vector of trial t.  → (cuts[trials], best index, x_best or None
+        (int8[n]), labels or None (int8[trials, n]))."""
+        self._need_round()
+        trials = int(trials)
+        g = _f64c(gauss)
+        if g.shape != (trials, self.r):
+            raise ValueError(f"gauss must have shape (trials, r) = ({trials}, {self.r}), got {g.shape}")
+        cuts = np.zeros(max(trials, 1))
+        best = C.c_int64(-1)
+        xb = np.zeros(self.n, dtype=np.int8) if want_best else None
+        lab = np.zeros((max(trials, 1), self.n), dtype=np.int8) if want_labels else None
+        self._ck(self.abi.round(self._h, int(mode), int(slot), trials, _pd(g), _pd(cuts), C.byref(best),
+                                xb.ctypes.data_as(_pi8) if want_best else None,
+                                lab.ctypes.data_as(_pi8) if want_labels else None))
+        return cuts[:trials], int(best.value), xb, (lab[:trials] if want_labels else None)
 
     # -- device timing ------------------------------------------------------------------------------
     def profile_enable(self, on: bool = True):

@@ -2,6 +2,7 @@
 // kernels in k_dense.h / k_sparse.h / k_scalar.h.  One solver handle = one SDP instance resident in
 // HBM + one HIP stream.  There is no CPU fallback: without a device every entry point fails.
 #include "../../include/sdplr_hip.h"
+#include "../../include/sdplr_hip_round.h"
 
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,7 @@
 #include "k_eig.h"
 #include "k_resident.h"
 #include "k_group.h"
+#include "k_round.h"
 
 namespace {
 
@@ -230,6 +232,16 @@ struct sdplr_hip_solver {
   // scratch arrays for operator calls on the caller's own matrices / vectors (SDPLR_F_SCRATCH, SDPLR_V_SCRATCH)
   double* scratchF[2] = {nullptr, nullptr};
   double* scratchV = nullptr;
+  // randomized rounding (k_round.h): the graph's upper triangle, and the call's work arrays — grown on demand and kept
+  struct Round {
+    bool have_graph = false;
+    long long E = 0;
+    int *ei = nullptr, *ej = nullptr;
+    double* ew = nullptr;
+    enum { LAB, KEYS, GT, PART, CUTS, SELK, SELCUT, OUT8, NBUF };
+    void* buf[NBUF] = {};
+    size_t cap[NBUF] = {};
+  } rd;
   // counters (sdplr_hip_get_stats)
   int64_t st_captures = 0, st_capture_failed = 0, st_capture_skipped = 0, st_graph_batches = 0,
           st_eager_batches = 0, st_lz_graph = 0, st_lz_eager = 0, st_iters = 0, st_rs_loops = 0, st_rs_lz = 0, st_rs_fg = 0, st_rs_shared = 0, st_pdrop = 0, st_grp_loops = 0, st_ring_loops = 0, st_ring_materialized = 0;
@@ -4411,6 +4423,155 @@ int32_t sdplr_hip_factor_dot(S* s, int32_t slot_a, int32_t slot_b, double* out) 
   if (rc) return rc;
   *out = s->hc->descent;
   return sync_check(s);
+}
+
+// ---- randomized rounding (include/sdplr_hip_round.h, k_round.h) ----------------------------------------------------
+// Both calls leave the solver's state alone: no NEED_FINAL_RW (the control block's shadow, G's consistency, a history in
+// ring form and the lazy dirt all stay as they are), nothing of the arena or the control block is written.  R is never in
+// ring form and is current in HBM on every route once the call that moved it has returned (get_factor reads it the same way).
+static int round_reserve(S* s, int k, size_t bytes) {
+  if (s->rd.buf[k] && s->rd.cap[k] >= bytes) return SDPLR_OK;
+  HIPCK(s, hipStreamSynchronize(s->stream));
+  dfree(s, s->rd.buf[k]);
+  s->rd.buf[k] = nullptr;
+  s->rd.cap[k] = 0;
+  char* p = nullptr;
+  const int rc = dalloc(s, &p, bytes);
+  if (rc) return rc;
+  s->rd.buf[k] = p;
+  s->rd.cap[k] = bytes;
+  return SDPLR_OK;
+}
+
+int32_t sdplr_hip_round_set_graph(S* s, int64_t base, int64_t nnz, const int64_t* I, const int64_t* J, const double* W) {
+  ApiShared api_guard(dev_of(s));
+  if (have_device() <= 0) return fail(nullptr, SDPLR_ERR_NO_DEVICE, "no usable HIP device (libsdplr_hip has no CPU fallback)");
+  NEED_FINAL(s);
+  if (nnz < 0 || (nnz > 0 && (!I || !J || !W))) return fail(s, SDPLR_ERR_INVALID_ARG, "round_set_graph: bad arguments");
+  std::vector<int> ei, ej;
+  std::vector<double> ew;
+  for (int64_t k = 0; k < nnz; k++) {
+    const int64_t i = I[k] - base, j = J[k] - base;
+    if (i < 0 || i >= s->n || j < 0 || j >= s->n) return fail(s, SDPLR_ERR_INVALID_ARG, "round_set_graph: index out of range");
+    if (i < j) { ei.push_back((int)i); ej.push_back((int)j); ew.push_back(W[k]); }
+  }
+  HIPCK(s, hipStreamSynchronize(s->stream));
+  dfree(s, s->rd.ei); dfree(s, s->rd.ej); dfree(s, s->rd.ew);
+  s->rd.ei = s->rd.ej = nullptr;
+  s->rd.ew = nullptr;
+  s->rd.have_graph = false;
+  s->rd.E = 0;
+  if (!ei.empty()) {
+    int rc;
+    if ((rc = dalloc(s, &s->rd.ei, ei.size())) || (rc = dalloc(s, &s->rd.ej, ej.size())) || (rc = dalloc(s, &s->rd.ew, ew.size()))) return rc;
+    if ((rc = h2d_copy(s, s->rd.ei, ei.data(), ei.size() * sizeof(int))) || (rc = h2d_copy(s, s->rd.ej, ej.data(), ej.size() * sizeof(int))) ||
+        (rc = h2d_copy(s, s->rd.ew, ew.data(), ew.size() * sizeof(double)))) return rc;
+  }
+  s->rd.E = (long long)ei.size();
+  s->rd.have_graph = true;
+  return SDPLR_OK;
+}
+
+int32_t sdplr_hip_round(S* s, int32_t mode, int32_t slot, int64_t trials, const double* gauss, double* cuts, int64_t* best,
+                        int8_t* x_best, int8_t* labels) {
+  ApiShared api_guard(dev_of(s));
+  if (have_device() <= 0) return fail(nullptr, SDPLR_ERR_NO_DEVICE, "no usable HIP device (libsdplr_hip has no CPU fallback)");
+  NEED_FINAL(s);
+  if (!s->rd.have_graph) return fail(s, SDPLR_ERR_STATE, "round: no graph (sdplr_hip_round_set_graph)");
+  if (mode != 0 && mode != 1) return fail(s, SDPLR_ERR_INVALID_ARG, "round: mode must be 0 (hyperplane) or 1 (bisection)");
+  if (trials < 1 || trials > 4096) return fail(s, SDPLR_ERR_INVALID_ARG, "round: 1 ≤ trials ≤ 4096");
+  if (!gauss || !cuts || !best) return fail(s, SDPLR_ERR_INVALID_ARG, "round: null argument");
+  const double* R = nullptr;
+  if (slot == SDPLR_F_RT) {
+    R = aslot(s->arena, AS_R);
+  } else {
+    const bool scratch = slot == SDPLR_F_SCRATCH || slot == SDPLR_F_SCRATCH + 1;
+    if (!scratch && factor_ptr(s, slot) != nullptr) {   // as get_factor: the other arena slots are read in their stored form
+      const int rc_d = ensure_dirt(s);
+      if (rc_d) return rc_d;
+    }
+    R = factor_ptr(s, slot);
+    if (!R) return fail(s, SDPLR_ERR_INVALID_ARG, "round: bad slot");
+  }
+  using Rd = S::Round;
+  const long long n = s->n, E = s->rd.E;
+  const int r = (int)s->r, T = (int)trials, W = (T + 63) / 64, Tpad = 64 * W;
+  const int nb_score = blocks_for(E, 64 * (SDPLR_NT / 64) * 4, SDPLR_ROUND_SCORE_NB);   // ≥ four groups of 64 edges per wave
+  int rc;
+  if ((rc = round_reserve(s, Rd::LAB, (size_t)n * W * sizeof(round_u64))) || (rc = round_reserve(s, Rd::GT, (size_t)r * Tpad * sizeof(double))) ||
+      (rc = round_reserve(s, Rd::PART, (size_t)nb_score * Tpad * sizeof(double))) || (rc = round_reserve(s, Rd::CUTS, (size_t)Tpad * sizeof(double)))) return rc;
+  if (mode == 1 && ((rc = round_reserve(s, Rd::KEYS, (size_t)n * 64 * sizeof(round_u64))) || (rc = round_reserve(s, Rd::SELK, 64 * sizeof(round_u64))) ||
+                    (rc = round_reserve(s, Rd::SELCUT, 64 * sizeof(long long))))) return rc;
+  round_u64* lab = (round_u64*)s->rd.buf[Rd::LAB];
+  round_u64* keys = (round_u64*)s->rd.buf[Rd::KEYS];
+  double* gT = (double*)s->rd.buf[Rd::GT];
+  double* part = (double*)s->rd.buf[Rd::PART];
+  double* dcuts = (double*)s->rd.buf[Rd::CUTS];
+  {
+    std::vector<double> h((size_t)r * Tpad, 0.0);   // Γ transposed: the 64 values of one k and one trial block side by side
+    for (int t = 0; t < T; t++)
+      for (int k = 0; k < r; k++) h[(size_t)k * Tpad + t] = gauss[(size_t)t * r + k];
+    if ((rc = h2d_copy(s, gT, h.data(), h.size() * sizeof(double)))) return rc;
+  }
+  const int nb_rows = blocks_for(n, SDPLR_NT, 2048), nb_proj = (int)((n + SDPLR_NT - 1) / SDPLR_NT);
+  if (mode == 0) {
+    ProfScope ps(s, "round_project");
+    k_round_project<0><<<dim3(nb_proj, W), SDPLR_NT, 0, s->stream>>>(R, n, r, gT, Tpad, T, 0, lab, W, nullptr);
+    HIPCK(s, hipGetLastError());
+  } else {
+    round_u64* selK = (round_u64*)s->rd.buf[Rd::SELK];
+    long long* selCut = (long long*)s->rd.buf[Rd::SELCUT];
+    const int nb_pack = blocks_for((n + 63) / 64, SDPLR_NT / 64, 2048);
+    for (int w = 0; w < W; w++) {   // trial block by trial block: the work array is n × 64 keys, not n × T
+      const int valid = std::min(64, T - 64 * w);
+      {
+        ProfScope ps(s, "round_project");
+        k_round_project<1><<<dim3(nb_proj, 1), SDPLR_NT, 0, s->stream>>>(R, n, r, gT, Tpad, T, w, lab, W, keys);
+        HIPCK(s, hipGetLastError());
+      }
+      {
+        ProfScope ps(s, "round_select");
+        k_round_select<<<valid, SDPLR_ROUND_SEL_NT, 0, s->stream>>>(keys, n, n / 2, selK, selCut);
+        HIPCK(s, hipGetLastError());
+      }
+      {
+        ProfScope ps(s, "round_pack");
+        k_round_pack<<<nb_pack, SDPLR_NT, 0, s->stream>>>(keys, n, valid, selK, selCut, lab, W, w);
+        HIPCK(s, hipGetLastError());
+      }
+    }
+  }
+  {
+    ProfScope ps(s, "round_score");
+    k_round_score<<<dim3(nb_score, W), SDPLR_NT, 0, s->stream>>>(s->rd.ei, s->rd.ej, s->rd.ew, E, lab, W, Tpad, part);
+    HIPCK(s, hipGetLastError());
+  }
+  {
+    ProfScope ps(s, "round_fold");
+    k_round_fold<<<(T + SDPLR_NT - 1) / SDPLR_NT, SDPLR_NT, 0, s->stream>>>(part, nb_score, Tpad, T, dcuts);
+    HIPCK(s, hipGetLastError());
+  }
+  HIPCK(s, hipMemcpyAsync(cuts, dcuts, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIPCK(s, hipStreamSynchronize(s->stream));
+  int64_t b = 0;
+  for (int t = 1; t < T; t++)
+    if (mode == 0 ? cuts[t] > cuts[b] : cuts[t] < cuts[b]) b = t;
+  *best = b;
+  for (int pass = 0; pass < 2; pass++) {
+    int8_t* dst = pass == 0 ? x_best : labels;
+    if (!dst) continue;
+    const int t0 = pass == 0 ? (int)b : 0, nt = pass == 0 ? 1 : T;
+    if ((rc = round_reserve(s, Rd::OUT8, (size_t)n * nt))) return rc;
+    signed char* out8 = (signed char*)s->rd.buf[Rd::OUT8];
+    {
+      ProfScope ps(s, "round_labels");
+      k_round_labels<<<nb_rows, SDPLR_NT, 0, s->stream>>>(lab, n, W, t0, nt, out8);
+      HIPCK(s, hipGetLastError());
+    }
+    HIPCK(s, hipMemcpyAsync(dst, out8, (size_t)n * nt, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(s, hipStreamSynchronize(s->stream));
+  }
+  return SDPLR_OK;
 }
 
 // ---- profiling ---------------------------------------------------------------------------------------

@@ -358,12 +358,14 @@ def sdplr_steps(data: SDPData, var: DeviceSolver, config: BurerMonteiroConfig, n
 
 def sdplr(C=None, As=None, b=None, r: int = 1, *, constraint_types=None,
           config: Optional[BurerMonteiroConfig] = None, data: Optional[SDPData] = None,
-          abi: Optional[CABI] = None, native_inner_loop: bool = True, **kwargs) -> dict:
+          abi: Optional[CABI] = None, native_inner_loop: bool = True, callback=None, **kwargs) -> dict:
     """``sdplr(C, As, b, r; kwargs...)`` (src/sdplr.jl:91-138).
 
     Runs on the MI355X library (``load_hip()``) unless an ``abi`` is injected (the test-suite
     injects the CPU oracle's ABI to pin the control flow; the product never does).  ``data`` may
-    replace ``(C, As, b)`` with an already-built ``SDPData`` (batched builders)."""
+    replace ``(C, As, b)`` with an already-built ``SDPData`` (batched builders).  ``callback(var, data)`` — the
+    reference runner's rounding hook (exps/test.jl:132) — runs after the solve on the live handle, before it is closed:
+    its value is returned as ``callback_res``, its wall time as ``callback_time``."""
     config = config if config is not None else BurerMonteiroConfig()
     for key, value in kwargs.items():                           # :102-108
         key = _ASCII_ALIASES.get(key, key)
@@ -379,6 +381,10 @@ def sdplr(C=None, As=None, b=None, r: int = 1, *, constraint_types=None,
     preprocess_dt = time.time() - t0
     try:
         ans = _sdplr(data, var, config, native_inner_loop=native_inner_loop)
+        if callback is not None:
+            tc = time.time()
+            ans["callback_res"] = callback(var, data)
+            ans["callback_time"] = time.time() - tc
     finally:
         var.close()
     ans["preprocess_time"] = preprocess_dt                      # :130-131
