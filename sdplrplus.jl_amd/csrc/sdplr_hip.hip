@@ -3015,26 +3015,19 @@ double wall_clock_hz() {   // rate of wall_clock64() on this device
   return hz;
 }
 // SDPLR_HIP_FORCE_GRAPH ("treat this instance as a large one": the tests' default) and SDPLR_HIP_NO_RESIDENT keep an
-// instance on the multi-launch routes.
-bool rs_loop_applies(const S* s, int armijo) {
-  if (!s->rs_ok || armijo || s->h < 1 || s->h > 4 || s->prof_on) return false;
-  if (s->force_graph || getenv("SDPLR_HIP_NO_RESIDENT") != nullptr) return false;
-  return rs_loop_lds(s) <= RS_LDS_MAX;
+// instance on the multi-launch routes, and so does per-kernel timing: what all four predicates below ask first.
+bool rs_route_open(const S* s, bool lanczos = false) {
+  if (s->prof_on || s->force_graph || getenv("SDPLR_HIP_NO_RESIDENT") != nullptr) return false;
+  return !lanczos || getenv("SDPLR_HIP_CLASSIC_LANCZOS") == nullptr;
 }
+bool rs_fg_applies(const S* s) { return rs_route_open(s) && s->rs_ok && rs_loop_lds(s) <= RS_LDS_MAX; }
+bool rs_loop_applies(const S* s, int armijo) { return rs_fg_applies(s) && !armijo && s->h >= 1 && s->h <= 4; }
 // the structured form: the instances of the resident loop (any rank), S = S(y) of the device's y
 bool rs_lanczos_ell_applies(const S* s) {
-  if (!s->rs_ok || !s->S_from_y || s->prof_on) return false;
-  if (s->force_graph || getenv("SDPLR_HIP_NO_RESIDENT") != nullptr || getenv("SDPLR_HIP_CLASSIC_LANCZOS") != nullptr) return false;
-  return (size_t)4 * s->n * sizeof(double) <= RS_LDS_MAX;
-}
-bool rs_fg_applies(const S* s) {
-  if (!s->rs_ok || s->prof_on) return false;
-  if (s->force_graph || getenv("SDPLR_HIP_NO_RESIDENT") != nullptr) return false;
-  return rs_loop_lds(s) <= RS_LDS_MAX;
+  return rs_route_open(s, true) && s->rs_ok && s->S_from_y && (size_t)4 * s->n * sizeof(double) <= RS_LDS_MAX;
 }
 bool rs_lanczos_applies(const S* s) {
-  if (s->force_graph || getenv("SDPLR_HIP_NO_RESIDENT") != nullptr || getenv("SDPLR_HIP_CLASSIC_LANCZOS") != nullptr) return false;
-  if (s->prof_on || !s->have_sparse || s->lr.ST > SDPLR_LRMAX) return false;
+  if (!rs_route_open(s, true) || !s->have_sparse || s->lr.ST > SDPLR_LRMAX) return false;
   int64_t max_nnz = 1 << 14;   // (12 bytes per entry from L2 at ≈ 67 GB/s per CU: beyond this two launches per step are faster)
   if (const char* e = getenv("SDPLR_HIP_RESIDENT_LZ_NNZ")) max_nnz = atoll(e);
   return s->nnzS <= max_nnz && (size_t)3 * s->n * sizeof(double) <= RS_LDS_MAX;
@@ -3077,24 +3070,115 @@ RsLoopArgs rs_loop_args(S* s, double time_budget_s, bool refresh_P, bool pre_lam
   a.budget_ticks = time_budget_s > 0 ? std::max<long long>(1, (long long)(time_budget_s * wall_clock_hz())) : 0;
   return a;
 }
-struct RsLoopIn {   // what a major iteration writes into the control block in front of its loop
-  double sigma, gtol, fprec, normC, normb;
-  int grel, prel;
-  long long max_iters;
+// ---- what the four drivers of the inner while loop share: parameters, entry, route choice, exit -----------------------
+// (inner_loop_impl: the multi-launch routes; run_resident_loop: one resident launch; sdplr_hip_batch_major_iteration: the
+// shared resident launch; run_edge_group: the shared edge-path launches)
+struct LoopParams {   // one loop's parameters: the scalar arguments of the C entry points, or a batch item
+  double sigma;       // var.σ[] of the major iteration (read only where the loop's parameters ride a launch: rs_loop_set_in)
+  double cur_gtol, fprec_eps, normC, normb;
+  int grel, prel, use_armijo;
+  long long max_local_iters;
+  double time_budget_s;
+  double L, gnorm, pvnorm;   // ℒ, ‖∇ℒ‖, ‖pv‖ at the loop's entry
 };
-void rs_loop_set_in(RsLoopArgs& a, const RsLoopIn& in) {
+LoopParams loop_params(double normC, double normb, int grel, int prel, int use_armijo, double sigma, double cur_gtol, double fprec_eps,
+                       long long max_local_iters, double time_budget_s, const double* L, const double* gn, const double* pn) {
+  return LoopParams{sigma, cur_gtol, fprec_eps, normC, normb, grel, prel, use_armijo, max_local_iters, time_budget_s,
+                    L ? *L : 0.0, gn ? *gn : 0.0, pn ? *pn : 0.0};
+}
+LoopParams loop_params(const sdplr_hip_major_item& q) {
+  return loop_params(q.normC, q.normb, q.gtol_relative, q.ptol_relative, q.use_armijo, q.sigma, q.cur_gtol, q.fprec_eps,
+                     q.max_local_iters, q.time_budget_s, &q.lagrangian, &q.grad_norm, &q.primal_vio_norm);
+}
+// … into the host shadow of the control block, in front of a loop of the multi-launch routes
+void loop_params_to_ctrl(DevCtrl* c, const LoopParams& p) {
+  c->done = 0; c->exit_reason = 0; c->err = 0; c->use_armijo = p.use_armijo;
+  c->iters = 0; c->max_iters = p.max_local_iters; c->reldelta_exit = 0; c->norms_pending = 0; c->pv2_extra = 0.0;
+  c->cur_gtol = p.cur_gtol; c->fprec_eps = p.fprec_eps; c->normC = p.normC; c->normb = p.normb;
+  c->grel = p.grel; c->prel = p.prel;
+  c->L = p.L; c->gnorm = p.gnorm; c->pvnorm = p.pvnorm; c->alpha = 0.0; c->alpha_max = 1.0;
+}
+// … and into the arguments of a resident launch, whose kernel writes them into its copy of the control block
+void rs_loop_set_in(RsLoopArgs& a, const LoopParams& p) {
   a.in_set = 1;
-  a.in_sigma = in.sigma; a.in_gtol = in.gtol; a.in_fprec = in.fprec; a.in_normC = in.normC; a.in_normb = in.normb;
-  a.in_grel = in.grel; a.in_prel = in.prel; a.in_max_iters = in.max_iters;
+  a.in_sigma = p.sigma; a.in_gtol = p.cur_gtol; a.in_fprec = p.fprec_eps; a.in_normC = p.normC; a.in_normb = p.normb;
+  a.in_grel = p.grel; a.in_prel = p.prel; a.in_max_iters = p.max_local_iters;
+}
+
+// Entry: what the last call left pending is settled and the control block is in the shadow, ready for the loop's
+// parameters.  The loop's first kernel overwrites dirt, so a pending dirt ← s_latest is dropped, not made (the caller puts
+// it back if not one iteration runs); keep_ring: the history stays in ring form (k_dense.h) for a loop that goes on with it.
+struct LoopEntry {
+  bool hc_was_valid, G_was_consistent;
+  int dirt_was_from;
+};
+int loop_enter(S* s, bool keep_ring, LoopEntry* e) {
+  *e = LoopEntry{s->hc_valid, s->G_consistent, s->dirt_from};
+  s->dirt_from = -1;
+  if (keep_ring) s->ring_on = false;   // (NEED_FINAL_RW leaves it alone)
+  NEED_FINAL_RW(s);
+  if (keep_ring) s->ring_on = true;
+  const bool gram_work = s->h > 0 && (s->gram_dirty || s->ynext_pending || s->sg_stale);
+  ensure_gram(s);
+  s->hc_valid = e->hc_was_valid && !gram_work;   // (nothing has been enqueued since the shadow was last in step)
+  const int rc = pull_if_stale(s);
+  s->hc_valid = false;
+  return rc;
+}
+
+// Route: which kernels run the loop and what is formed from scratch in front of it — a function of the handle's state.
+int64_t p_refresh_iters() {   // iterations P (and a carried G) may be updated incrementally before they are formed from scratch
+  static const int64_t k = getenv("SDPLR_HIP_P_REFRESH_ITERS") ? atoll(getenv("SDPLR_HIP_P_REFRESH_ITERS")) : 256;
+  return k;
 }
 // the resident loop without P (k_resident.h, PDROP): A_g is the cost matrix
 bool rs_can_drop_P(const S* s) { return s->ff.gid_g == (int)s->m && !s->no_pdrop; }
-int enq_resident_loop(S* s, double time_budget_s, bool refresh_P, bool pre_lambda = false, bool pre_clear_fg = false,
-                      const RsLoopIn* in = nullptr, bool pdrop = false) {
-  RsLoopArgs a = rs_loop_args(s, time_budget_s, refresh_P, pre_lambda, pre_clear_fg);
-  if (in) rs_loop_set_in(a, *in);
+enum LoopKind { LOOP_GENERIC, LOOP_EDGE, LOOP_FAST, LOOP_FAST2, LOOP_RESIDENT };
+struct LoopRoute {
+  LoopKind kind;
+  bool pdrop;        // the P-less kernels: G is carried forward from G_old
+  bool refresh_G;    // … after g! from scratch in front of the loop (the carried G has reached the refresh interval)
+  bool refresh_P;    // P = A_g·R from scratch in front of the loop
+  bool ring;         // history in ring form (k_dense.h)
+  int team_w;        // workgroups per instance (resident, P-less: k_resident.h, TEAM)
+  bool prologue;     // λ update / lbfgs_clear! / fg! ride the resident launch: G and P are fresh, the history is empty
+  bool lazy_dirt;    // lbfgs_update! rides another kernel, which leaves `dirt *= α` to a copy dirt ← s_latest (ensure_dirt)
+  bool shared;       // the launches are shared with other instances (set by the batch entry point)
+};
+// The P-less kernels carry G forward: only from a G known to be the gradient at the device's state (G_was_consistent, or
+// the fg! of the prologue), and only for so many steps before G is formed from scratch again — by g! in front of a
+// multi-launch loop, by a call of the P-based kernel, which rebuilds G at every step, on the resident route.
+// resume (SDPLR_MAJOR_RESUME): the continuation of a capped loop takes the kernel the capped call took and refreshes
+// nothing by age, so that cap + resume ≡ one uncapped call, bit for bit.
+LoopRoute choose_loop_route(const S* s, int use_armijo, bool resume, bool G_was_consistent, bool with_prologue) {
+  const int64_t age = p_refresh_iters();
+  LoopRoute rt{};
+  rt.team_w = 1;
+  if (rs_loop_applies(s, use_armijo)) {
+    rt.kind = LOOP_RESIDENT;
+    rt.prologue = with_prologue;
+    rt.pdrop = rs_can_drop_P(s) && (with_prologue || (G_was_consistent && (resume ? s->pdrop_now : s->G_age < age)));
+    rt.refresh_P = with_prologue || !s->P_valid || (!resume && s->P_age >= age);   // (fg! rebuilds P = A_g·R itself)
+    if (rt.pdrop) rt.team_w = rs_team_w(s);
+    return rt;
+  }
+  const bool fast2 = s->fast && s->fast_singleton && !use_armijo;
+  rt.kind = fast2 ? LOOP_FAST2 : s->fast ? LOOP_FAST : edge_applies(s, use_armijo) ? LOOP_EDGE : LOOP_GENERIC;
+  rt.pdrop = fast2 && step_can_drop_P(s) && G_was_consistent && (!resume || s->pdrop_now);
+  rt.refresh_G = rt.pdrop && !resume && s->G_age >= age;
+  rt.refresh_P = s->fast && !rt.pdrop && (!s->P_valid || (!resume && s->P_age >= age));
+  // (a ring is entered on whatever history is stored: k_dense.h)
+  rt.ring = fast2 && (rt.pdrop ? ring_shape_ok(s) : ring_shape_pb_ok(s));
+  rt.lazy_dirt = s->fast ? step_fuses_update(s) : spmm_fuses_update(s);
+  return rt;
+}
+
+int enq_resident_loop(S* s, const LoopParams& p, const LoopRoute& rt, bool pre_lambda) {
+  RsLoopArgs a = rs_loop_args(s, p.time_budget_s, rt.refresh_P, pre_lambda, rt.prologue);
+  if (rt.prologue) rs_loop_set_in(a, p);   // (otherwise the caller has pushed the control block)
   const size_t lds = rs_loop_lds(s);
-  const int W = pdrop ? rs_team_w(s) : 1;
+  const int W = rt.team_w;
+  const bool pdrop = rt.pdrop;
   if (W > 1) {   // a team: W workgroups of one XCD (blocks 0, 8, …: k_resident.h)
     a.team_w = W;
     a.xch = s->rs_xch;
@@ -3104,7 +3188,6 @@ int enq_resident_loop(S* s, double time_budget_s, bool refresh_P, bool pre_lambd
   } else if (pdrop) { RS_VEC_DISPATCH(s, ({ RS_SET_ATTR((k_rs_loop<VEC, 4, true>)); k_rs_loop<VEC, 4, true><<<1, SDPLR_RS_NT, lds, s->stream>>>(a); })) }
   else { RS_VEC_DISPATCH(s, ({ RS_SET_ATTR((k_rs_loop<VEC, 4, false>)); k_rs_loop<VEC, 4, false><<<1, SDPLR_RS_NT, lds, s->stream>>>(a); })) }
   HIPCK(s, hipGetLastError());
-  s->st_rs_loops++;
   return SDPLR_OK;
 }
 
@@ -3125,62 +3208,74 @@ static int park_ynext_after_not_descent(S* s, int latest) {
   return SDPLR_OK;
 }
 
-// launch + wait + the host-side bookkeeping of one resident loop (the control block has been pushed by the caller);
-// pre_lambda / pre_clear_fg: the head of a major iteration rides the same launch (sdplr_hip_major_iteration)
-int run_resident_loop(S* s, double time_budget_s, bool pre_lambda, bool pre_clear_fg, double* Lio, double* gnio, double* pnio,
-                      double* last_alpha, int64_t* iters, int32_t* exit_reason, const RsLoopIn* in = nullptr,
-                      bool G_was_consistent = false, bool resume = false) {
-  static const int64_t refresh_iters = getenv("SDPLR_HIP_P_REFRESH_ITERS") ? atoll(getenv("SDPLR_HIP_P_REFRESH_ITERS")) : 256;
-  // without P: G is carried forward from the fg! of the prologue, or from a G known to be the gradient at the device's
-  // state and not older than the refresh interval (otherwise this call runs the P-based loop, which rebuilds G at every step).
-  // resume (SDPLR_MAJOR_RESUME): the continuation of a capped loop takes the kernel the capped call took and refreshes
-  // nothing by age, so that cap + resume ≡ one uncapped call, bit for bit.
-  const bool pdrop = rs_can_drop_P(s) && (pre_clear_fg || (G_was_consistent && (resume ? s->pdrop_now : s->G_age < refresh_iters)));
-  const bool refresh = pre_clear_fg || !s->P_valid || (!resume && s->P_age >= refresh_iters);   // (fg! rebuilds P = A_g·R itself)
-  int rc = enq_resident_loop(s, time_budget_s, refresh, pre_lambda, pre_clear_fg, in, pdrop);
+// Exit: the handle's bookkeeping behind a loop whose closing control block (or result row) is on the host.  What belongs
+// to one route alone — the ring's scalars, the relaunch without a team — has been settled by its driver.
+struct LoopOutcome {
+  int64_t iters;
+  int why, err;
+  int latest;   // lbfgs latest of the closing block (−1: no block at hand — read by the routes with a lazy dirt only)
+};
+int loop_leave(S* s, const LoopRoute& rt, const LoopOutcome& o) {
+  // the error exits leave err / done set in the device's block: cleared, so that the handle carries on
+  auto clear_error = [&]() {
+    const int rc = pull_if_stale(s);
+    if (rc) return rc;
+    s->hc->err = 0; s->hc->done = 0;
+    return push(s);
+  };
+  s->pdrop_now = rt.pdrop;
+  if (rt.pdrop) s->P_valid = false;          // P is neither read nor kept up to date by this loop
+  else if (rt.refresh_P) s->P_valid = true;
+  if (rt.kind != LOOP_GENERIC) { s->S_stale = true; s->S_from_y = true; }   // y is current, S is assembled by whoever reads it next (ensure_S)
+  if (rt.prologue) { s->st_rs_fg++; s->gram_dirty = false; }
+  if (rt.kind == LOOP_RESIDENT) { s->st_rs_loops++; if (rt.shared) s->st_rs_shared++; }
+  if (rt.ring) s->st_ring_loops++;
+  if (o.err == SDPLR_ERR_TEAM_TIMEOUT) {
+    (void)clear_error();
+    return fail(s, SDPLR_ERR_HIP, "resident loop: a team member never arrived at a barrier (the grid was not co-resident)");
+  }
+  s->P_age = (rt.refresh_P ? 0 : s->P_age) + o.iters;
+  // (the P-based kernels form G from P and y at every step)
+  s->G_age = rt.pdrop ? ((rt.refresh_G || rt.prologue) ? 0 : s->G_age) + o.iters : 0;
+  // G was rewritten by g! after the last update when the loop left through the relative-decrease exit (no lbfgs_update!,
+  // src/sdplr.jl:239-241): the dots with G are stale then.  (The resident kernel leaves `dirt *= α`, src/lbfgs.jl:142,
+  // itself; after the fg! of a prologue and no iteration the dots are those of a cleared history: zero, exact.)
+  s->sg_stale = (o.why == EXIT_RELDELTA);
+  s->ynext_pending = (o.why == EXIT_RELDELTA) && s->h > 0;
+  if (rt.lazy_dirt && o.iters > 0 && o.err == 0 && o.why != EXIT_RELDELTA) s->dirt_from = o.latest - 1;
+  if (o.err == SDPLR_ERR_NOT_DESCENT) {
+    int rc = clear_error();
+    if (!rc) rc = park_ynext_after_not_descent(s, s->hc->latest);
+    return rc ? rc : fail(s, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
+  }
+  s->st_iters += o.iters;
+  if (rt.pdrop) s->st_pdrop++;
+  if (rt.kind == LOOP_EDGE && rt.shared) s->st_grp_loops++;
+  s->G_consistent = true;   // g! has run at the loop's last point
+  return SDPLR_OK;
+}
+
+// launch + wait + exit of one resident loop.  Without a prologue the control block has been pushed by the caller; with
+// one, the head of a major iteration and the loop's parameters ride the same launch (sdplr_hip_major_iteration).
+int run_resident_loop(S* s, const LoopParams& p, LoopRoute rt, bool pre_lambda, double* Lio, double* gnio, double* pnio,
+                      double* last_alpha, int64_t* iters, int32_t* exit_reason) {
+  int rc = enq_resident_loop(s, p, rt, pre_lambda);
   if (rc) return rc;
-  s->pdrop_now = pdrop;
-  s->P_valid = !pdrop;
-  if (refresh) s->P_age = 0;
-  if (pre_clear_fg || !pdrop) s->G_age = 0;
-  s->S_stale = true;   // y is current, S is assembled by whoever reads it next (ensure_S)
-  s->S_from_y = true;
-  if (pre_clear_fg) { s->st_rs_fg++; s->gram_dirty = false; }
   if ((rc = pull_blocking(s))) return rc;
   DevCtrl* c = s->hc;
   if (c->err == SDPLR_ERR_TEAM_PLACEMENT) {   // the members were not dealt to one XCD: nothing was touched — once more, without a team
     c->err = 0;
     s->no_team = true;
+    rt.team_w = 1;
     if ((rc = push(s))) return rc;
-    if ((rc = enq_resident_loop(s, time_budget_s, refresh, pre_lambda, pre_clear_fg, in, pdrop))) return rc;
-    s->st_rs_loops--;
+    if ((rc = enq_resident_loop(s, p, rt, pre_lambda))) return rc;
     if ((rc = pull_blocking(s))) return rc;
   }
-  if (c->err == SDPLR_ERR_TEAM_TIMEOUT) {
-    c->err = 0; c->done = 0;
-    (void)push(s);
-    return fail(s, SDPLR_ERR_HIP, "resident loop: a team member never arrived at a barrier (the grid was not co-resident)");
-  }
-  const int why_rs = c->exit_reason;
-  // (`dirt *= α`, src/lbfgs.jl:142: the kernel itself left dirt = s_latest)
-  // no iteration ran after the fg! of the prologue: the dots with G are those of a cleared history (zero, exact)
-  s->sg_stale = (why_rs == EXIT_RELDELTA);
-  s->ynext_pending = (why_rs == EXIT_RELDELTA) && s->h > 0;
-  if (c->err == SDPLR_ERR_NOT_DESCENT) {
-    const int latest_ = c->latest;
-    c->err = 0; c->done = 0;
-    (void)push(s);
-    if ((rc = park_ynext_after_not_descent(s, latest_))) return rc;
-    return fail(s, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
-  }
-  s->st_iters += c->iters;
-  s->P_age += c->iters;
-  if (pdrop) { s->G_age += c->iters; s->st_pdrop++; }
-  s->G_consistent = true;
+  if ((rc = loop_leave(s, rt, LoopOutcome{c->iters, c->exit_reason, c->err, c->latest}))) return rc;
   *Lio = c->L; *gnio = c->gnorm; *pnio = c->pvnorm;
   if (last_alpha) *last_alpha = c->alpha;
   if (iters) *iters = c->iters;
-  if (exit_reason) *exit_reason = why_rs;
+  if (exit_reason) *exit_reason = c->exit_reason;
   return SDPLR_OK;   // (pull_blocking has drained the stream and checked the launch)
 }
 
@@ -3273,6 +3368,38 @@ void note_capture_failure(S* s, const char* what) {
     said = true;
     fprintf(stderr, "[sdplr_hip] warning: %s\n", s->err.c_str());
   }
+}
+// `body`'s launches on the handle's stream as one instantiated graph in *out.  Capture is fragile on ROCm 7.2 when OTHER
+// host threads issue HIP calls meanwhile (observed: 8 handles driven by 8 threads → "operation failed due to a previous
+// error during capture", any capture mode).  So: one capture at a time, under the process-wide lock taken exclusively —
+// with a bounded wait (other handles may sit in their own inner loops for seconds): no lock in time ⇒ *out stays null,
+// this call launches eagerly and the next call tries again.  A capture that FAILS is not an error either, but it is
+// recorded (note_capture_failure) and this handle launches eagerly for good.
+template <typename Body>
+void capture_graph(S* s, ApiLock* api_lock, const char* what, hipGraphExec_t* out, Body&& body) {
+  api_lock->unlock();
+  {
+    std::unique_lock<ApiMutex> excl(g_api_rw, std::chrono::milliseconds(capture_wait_ms()));
+    if (!excl.owns_lock()) {
+      s->st_capture_skipped++;
+    } else {
+      hipGraph_t graph = nullptr;
+      bool ok = hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed) == hipSuccess;
+      if (ok) {
+        body();
+        ok = hipStreamEndCapture(s->stream, &graph) == hipSuccess && graph != nullptr;
+      }
+      if (ok) ok = hipGraphInstantiate(out, graph, nullptr, nullptr, 0) == hipSuccess;
+      if (graph) (void)hipGraphDestroy(graph);
+      if (ok) {
+        s->st_captures++;
+      } else {
+        note_capture_failure(s, what);
+        *out = nullptr;
+      }
+    }
+  }
+  api_lock->lock();
 }
 
 // hub-row blocks inside k_lz_band's grid: four rows per 1024-thread block, at most 64 blocks (the band plan leaves
@@ -3424,30 +3551,8 @@ int run_lanczos(S* s, int64_t q, const double* v0, double* alpha, double* beta, 
   bool use_graph = !s->prof_on && !s->graph_disabled && getenv("SDPLR_HIP_NO_GRAPH") == nullptr && (n >= (1 << 14) || s->force_graph) &&
                    s->lz_band_now == s->use_band;   // (the captured steps are the band plan's when there is one)
   if (use_graph && !s->lz_graph && api_lock) {
-    api_lock->unlock();
-    {
-      std::unique_lock<ApiMutex> excl(g_api_rw, std::chrono::milliseconds(capture_wait_ms()));
-      if (!excl.owns_lock()) {
-        s->st_capture_skipped++;   // busy: this call launches eagerly, the next one tries again
-      } else {
-        hipGraph_t graph = nullptr;
-        bool ok = hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed) == hipSuccess;
-        if (ok) {
-          for (int t = 0; t < reps; t++) three();
-          ok = hipStreamEndCapture(s->stream, &graph) == hipSuccess && graph != nullptr;
-        }
-        if (ok) ok = hipGraphInstantiate(&s->lz_graph, graph, nullptr, nullptr, 0) == hipSuccess;
-        s->lz_graph_reps = reps;
-        if (graph) (void)hipGraphDestroy(graph);
-        if (ok) {
-          s->st_captures++;
-        } else {
-          note_capture_failure(s, "Lanczos");
-          s->lz_graph = nullptr;
-        }
-      }
-    }
-    api_lock->lock();
+    capture_graph(s, api_lock, "Lanczos", &s->lz_graph, [&] { for (int t = 0; t < reps; t++) three(); });
+    s->lz_graph_reps = reps;
   }
   if (!s->lz_graph) use_graph = false;
   if (use_graph) {
@@ -3811,96 +3916,56 @@ int32_t sdplr_hip_linesearch_armijo(S* s, double alpha_max, double* alpha, doubl
 }
 
 // ---- the inner loop ----------------------------------------------------------------------------------
-static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, int32_t prel, int32_t use_armijo,
-                               double cur_gtol, double fprec_eps, int64_t max_local_iters, double time_budget_s,
-                               double* Lio, double* gnio, double* pnio, double* last_alpha, int64_t* iters,
-                               int32_t* exit_reason, bool resume);
-int32_t sdplr_hip_inner_loop(S* s, double normC, double normb, int32_t grel, int32_t prel, int32_t use_armijo,
-                             double cur_gtol, double fprec_eps, int64_t max_local_iters, double time_budget_s,
-                             double* Lio, double* gnio, double* pnio, double* last_alpha, int64_t* iters,
-                             int32_t* exit_reason) {
-  return inner_loop_impl(s, normC, normb, grel, prel, use_armijo, cur_gtol, fprec_eps, max_local_iters, time_budget_s, Lio, gnio,
-                         pnio, last_alpha, iters, exit_reason, false);
-}
-static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, int32_t prel, int32_t use_armijo,
-                               double cur_gtol, double fprec_eps, int64_t max_local_iters, double time_budget_s,
-                               double* Lio, double* gnio, double* pnio, double* last_alpha, int64_t* iters,
-                               int32_t* exit_reason, bool resume) {
+static int32_t inner_loop_impl(S* s, const LoopParams& p, double* Lio, double* gnio, double* pnio, double* last_alpha,
+                               int64_t* iters, int32_t* exit_reason, bool resume) {
   ApiLock api_lock(g_api_rw);
   bind_device(dev_of(s));
-  const bool hc_was_valid = s && s->finalized && s->hc_valid;
-  const bool G_was_consistent = s && s->finalized && s->G_consistent;
-  // (the loop's first kernel after the seam overwrites dirt: a pending dirt ← s_latest is dropped, not made — unless the
-  // loop turns out not to run a single iteration, see below)
-  const int dirt_was_from = (s && s->finalized) ? s->dirt_from : -1;
-  // Ring form of the history (k_dense.h): kept across calls while nothing else has touched the arena.  Decided before
-  // NEED_FINAL_RW, which would turn a ring back into the stored form.
-  bool ring_keep = false;
-  if (s && s->finalized && s->ring_on) {
-    const bool fast2_ = s->fast && s->fast_singleton && !use_armijo;
-    static const int64_t refresh_iters_ = getenv("SDPLR_HIP_P_REFRESH_ITERS") ? atoll(getenv("SDPLR_HIP_P_REFRESH_ITERS")) : 256;
-    // (a P-less loop due for its refresh of G writes G at its own place: not on a ring)
-    const bool would_pdrop = fast2_ && step_can_drop_P(s) && s->G_consistent && (!resume || s->pdrop_now);
-    const bool refresh_due = would_pdrop && !resume && s->G_age >= refresh_iters_;
-    ring_keep = fast2_ && ring_shape_common(s) && !refresh_due && !s->ring_unc && Lio && gnio && pnio &&
-                max_local_iters >= 1 && !rs_loop_applies(s, use_armijo) &&
-                !(s->gram_dirty || s->ynext_pending || s->sg_stale);
-    if (ring_keep) s->ring_on = false;   // (NEED_FINAL_RW leaves it alone; set again below)
+  if (!s || !s->finalized || !Lio || !gnio || !pnio || p.max_local_iters < 1) {
+    NEED_FINAL_RW(s);
+    return fail(s, SDPLR_ERR_INVALID_ARG, "inner_loop: bad args");
   }
-  if (s && s->finalized && max_local_iters >= 1 && Lio && gnio && pnio) s->dirt_from = -1;
-  NEED_FINAL_RW(s);
-  if (ring_keep) s->ring_on = true;
-  if (!Lio || !gnio || !pnio || max_local_iters < 1) return fail(s, SDPLR_ERR_INVALID_ARG, "inner_loop: bad args");
-  const bool gram_work = s->h > 0 && (s->gram_dirty || s->ynext_pending || s->sg_stale);
-  ensure_gram(s);
+  const int use_armijo = p.use_armijo;
+  const int64_t max_local_iters = p.max_local_iters;
+  const double time_budget_s = p.time_budget_s;
+  // (an instance that was set up for the resident route builds its tiles at its first multi-launch loop: the route reads
+  // their shape)
   int rc = rs_loop_applies(s, use_armijo) ? SDPLR_OK : tile_lds_attr(s);
   if (rc) return rc;
-  s->hc_valid = hc_was_valid && !gram_work;   // (nothing has been enqueued since the shadow was last in step)
-  if ((rc = pull_if_stale(s))) return rc;
-  s->hc_valid = false;
+  const LoopRoute rt = choose_loop_route(s, use_armijo, resume, s->G_consistent, false);
+  // Ring form of the history (k_dense.h): kept across calls while nothing else has touched the arena, for a loop that goes on
+  // with it.  (A P-less loop due for its refresh of G writes G at its own place: it enters a ring of its own.)
+  const bool ring_keep = s->ring_on && rt.ring && !rt.refresh_G && !s->ring_unc &&
+                         !(s->gram_dirty || s->ynext_pending || s->sg_stale);
+  LoopEntry e;
+  if ((rc = loop_enter(s, ring_keep, &e))) return rc;
   DevCtrl* c = s->hc;
-  c->done = 0; c->exit_reason = 0; c->err = 0; c->use_armijo = use_armijo;
-  c->iters = 0; c->max_iters = max_local_iters; c->reldelta_exit = 0; c->norms_pending = 0; c->pv2_extra = 0.0;
-  c->cur_gtol = cur_gtol; c->fprec_eps = fprec_eps; c->normC = normC; c->normb = normb;
-  c->grel = grel; c->prel = prel;
-  c->L = *Lio; c->gnorm = *gnio; c->pvnorm = *pnio; c->alpha = 0.0; c->alpha_max = 1.0;
+  loop_params_to_ctrl(c, p);
   // (no wait: the kernels are ordered behind the copy on the stream, and the host does not touch its shadow again before
   // the closing snapshot has been waited for)
   HIPCK(s, hipMemcpyAsync(s->ctrl, s->hc, sizeof(DevCtrl), hipMemcpyHostToDevice, s->stream));
+  if (rt.kind == LOOP_RESIDENT) {
+    // resident route (k_resident.h): the whole while loop is ONE launch of one workgroup; every exit — the time
+    // budget too — is taken on the device, the host reads the control block once
+    s->dirt_from = e.dirt_was_from;   // (the resident kernel leaves dirt itself: a pending copy from a multi-launch loop is made first)
+    if ((rc = ensure_dirt(s))) return rc;
+    return run_resident_loop(s, p, rt, false, Lio, gnio, pnio, last_alpha, iters, exit_reason);
+  }
   // Iterations are enqueued in batches — a captured hipGraph of `graph_iters` passes of the while
   // body, or eager launches when per-kernel event timing is on.  The device decides every exit;
   // once `done` is set the remaining kernels of a batch fall through.  The control block is
   // snapshotted after each batch, and batch k+1 is already queued while the host inspects the
   // snapshot of batch k, so the GPU never waits for the host.
-  if (rs_loop_applies(s, use_armijo)) {
-    // resident route (k_resident.h): the whole while loop is ONE launch of one workgroup; every exit — the time
-    // budget too — is taken on the device, the host reads the control block once
-    s->dirt_from = dirt_was_from;   // (the resident kernel leaves dirt itself: a pending copy from a multi-launch loop is made first)
-    if ((rc = ensure_dirt(s))) return rc;
-    return run_resident_loop(s, time_budget_s, false, false, Lio, gnio, pnio, last_alpha, iters, exit_reason, nullptr, G_was_consistent, resume);
-  }
-  const bool fastp = s->fast;
-  const bool fast2 = fastp && s->fast_singleton && !use_armijo;
-  static const int64_t refresh_iters = getenv("SDPLR_HIP_P_REFRESH_ITERS") ? atoll(getenv("SDPLR_HIP_P_REFRESH_ITERS")) : 256;
-  // the P-less step kernel carries G forward: only from a G known to be the gradient at the device's state, and only for
-  // so many steps before G is formed from scratch again (every fg! does that anyway)
-  // (resume — SDPLR_MAJOR_RESUME — continues a capped loop: the kernel the capped call took, and nothing refreshed by age, so
-  // that cap + resume ≡ one uncapped call bit for bit)
-  s->pdrop_now = fast2 && step_can_drop_P(s) && G_was_consistent && (!resume || s->pdrop_now);
-  if (s->pdrop_now && !resume && s->G_age >= refresh_iters) {
+  const bool fastp = s->fast, fast2 = rt.kind == LOOP_FAST2, edgep = rt.kind == LOOP_EDGE;
+  s->pdrop_now = rt.pdrop;   // (the enqueue functions read both)
+  s->ring_now = rt.ring;
+  if (rt.refresh_G) {
     enq_g(s, 0, false);          // g! from scratch (src/coreop.jl:305-317): same y, S assembled, G = 2·R·S
     s->S_stale = false;
-    s->G_age = 0;
   }
-  // (a ring is entered on whatever history is stored: k_dense.h)
-  s->ring_now = fast2 && (s->pdrop_now ? ring_shape_ok(s) : ring_shape_pb_ok(s));
   if (getenv("SDPLR_HIP_DEBUG"))
     fprintf(stderr, "[sdplr_hip] inner_loop: ring %d (kept %d, pdrop %d, shape %d: can_drop %d n_extra %d VEC %d LPR %d tile %d/%d nb_tile %d)\n",
             (int)s->ring_now, (int)ring_keep, (int)s->pdrop_now, (int)ring_shape_ok(s), (int)step_can_drop_P(s), s->n_extra,
             s->VEC, s->LPR, (int)s->use_tile, s->tile_lpr, s->nb_tile);
-  if (s->ring_on && !s->ring_now) {   // (a ring kept for a loop that turns out not to take it)
-    if ((rc = ensure_canonical(s))) return rc;
-  }
   {
     const bool fresh = s->ring_now && !s->ring_on;
     const int was = c->ring_on;
@@ -3910,23 +3975,24 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
       memset(c->ring_alpha, 0, sizeof c->ring_alpha);
     }
     c->ring_on = s->ring_now ? 1 : 0;
-    // (the control block went to the device above, before the route was known: the ring's scalars follow it)
+    // (the ring's scalars follow the control block, which went to the device above)
     if (fresh || was != c->ring_on)
       HIPCK(s, hipMemcpyAsync(&s->ctrl->ring_on, &c->ring_on, sizeof(DevCtrl) - offsetof(DevCtrl, ring_on), hipMemcpyHostToDevice, s->stream));
     s->ring_on = s->ring_now;
   }
   // From here to the closing pull the handle's ring scalars (ring_k … ring_alpha) are those of an EARLIER ring, or zeros: a
   // return in between must not leave the handle claiming ring form — the next look would materialise from them.  No valid
-  // control block exists on such a return (a HIP call failed): the arena is taken as it lies, the Gram data as unknown.
+  // control block exists on such a return (a HIP call failed): the arena is taken as it lies, the Gram data as unknown,
+  // and P as not kept up to date.
   auto bail = [&](int rc_) {
     s->ring_on = false;
     s->gram_dirty = true;
     s->G_consistent = false;
     s->hc_valid = false;
+    if (rt.pdrop) s->P_valid = false;
     return rc_;
   };
   const int ar = use_armijo ? 1 : (s->ring_now ? (s->pdrop_now ? 3 : 4) : (s->pdrop_now ? 2 : 0));
-  const bool edgep = !fastp && edge_applies(s, use_armijo);
   auto enq_iter = [&]() {
     if (fast2) enq_iteration_fast2(s);
     else if (fastp) enq_iteration_fast(s, use_armijo);
@@ -3936,50 +4002,13 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
   // the structured loops leave y current and S unassembled: said before the first enqueue, so that an error return on the
   // way cannot leave a stale S marked as assembled
   if (fastp || edgep) { s->S_stale = true; s->S_from_y = true; }
-  if (s->pdrop_now) {
-    s->P_valid = false;          // P is neither read nor kept up to date by this loop
-  } else if (fastp) {
-    if (!s->P_valid || (!resume && s->P_age >= refresh_iters)) {
-      enq_fast_refresh_P(s);
-      s->P_valid = true;
-      s->P_age = 0;
-    }
-  }
+  if (rt.refresh_P) enq_fast_refresh_P(s);
   // hipGraph batches pay for their capture (milliseconds, and exclusive of every other handle's HIP calls) only
   // on instances whose solve is long: small factors (config 5's n = 800 batch: 64 solves 1.3 → 0.95 s) stay eager
   bool use_graph = !s->prof_on && !s->graph_disabled && max_local_iters >= 4 && getenv("SDPLR_HIP_NO_GRAPH") == nullptr &&
                    (s->N >= (1LL << 17) || s->force_graph);
-  if (use_graph && !s->graph_exec[ar]) {
-    // Capture is fragile on ROCm 7.2 when OTHER host threads issue HIP calls meanwhile (observed: 8 handles
-    // driven by 8 threads → "operation failed due to a previous error during capture", any capture mode).
-    // So: one capture at a time, under the process-wide lock taken exclusively — with a bounded wait (other
-    // handles may sit in their own inner loops for seconds): no lock in time ⇒ this call runs eagerly and the
-    // next call tries again.  A capture that FAILS is not an error either, but it is recorded
-    // (note_capture_failure) and this handle launches eagerly for good.
-    api_lock.unlock();
-    {
-      std::unique_lock<ApiMutex> excl(g_api_rw, std::chrono::milliseconds(capture_wait_ms()));
-      if (!excl.owns_lock()) {
-        s->st_capture_skipped++;
-      } else {
-        hipGraph_t graph = nullptr;
-        bool ok = hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed) == hipSuccess;
-        if (ok) {
-          for (int i = 0; i < s->graph_iters; i++) enq_iter();
-          ok = hipStreamEndCapture(s->stream, &graph) == hipSuccess && graph != nullptr;
-        }
-        if (ok) ok = hipGraphInstantiate(&s->graph_exec[ar], graph, nullptr, nullptr, 0) == hipSuccess;
-        if (graph) (void)hipGraphDestroy(graph);
-        if (ok) {
-          s->st_captures++;
-        } else {
-          note_capture_failure(s, "inner loop");
-          s->graph_exec[ar] = nullptr;
-        }
-      }
-    }
-    api_lock.lock();
-  }
+  if (use_graph && !s->graph_exec[ar])
+    capture_graph(s, &api_lock, "inner loop", &s->graph_exec[ar], [&] { for (int i = 0; i < s->graph_iters; i++) enq_iter(); });
   if (!s->graph_exec[ar]) use_graph = false;
   // the time budget starts here: after any wait for the capture lock
   const auto t0 = std::chrono::steady_clock::now();
@@ -4068,9 +4097,7 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
   }
   // fold the partials of a last lbfgs_update (time-budget exit); a replayed graph does not pass through the
   // enqueue functions, so the producer's partial count is set here, not inherited
-  const bool loop_fused = fastp ? step_fuses_update(s) : spmm_fuses_update(s);   // lbfgs_update! rode another kernel
-  s->gram_nb = !loop_fused ? s->nb_upd : (fastp ? s->nb_step : spmm_upd_blocks(s));
-  if (fastp || edgep) { s->S_stale = true; s->S_from_y = true; }   // y is current, S is assembled by whoever reads it next (ensure_S)
+  s->gram_nb = !rt.lazy_dirt ? s->nb_upd : (fastp ? s->nb_step : spmm_upd_blocks(s));
   if (final_snap >= 0) {
     // the device closed the plan itself: the closing seam (Gram fold + loop tests) ran in front of this snapshot, nothing
     // has been enqueued behind it — it IS the control block (one launch, one copy and one wait less per call)
@@ -4085,44 +4112,28 @@ static int32_t inner_loop_impl(S* s, double normC, double normb, int32_t grel, i
   if (s->ring_now) {
     s->ring_k = c->ring_k; s->ring_n = c->ring_n; s->ring_unc = c->ring_unc; s->ring_latest = c->latest; s->ring_j0 = c->ring_j0;
     memcpy(s->ring_alpha, c->ring_alpha, sizeof s->ring_alpha);
+    // lbfgs_dir! ran, the step did not: the direction lies at position ring_k (unc = 2: k_ring_materialize)
+    if (c->err == SDPLR_ERR_NOT_DESCENT) s->ring_unc = 2;
   }
   if (c->done) why = c->exit_reason;   // the device's verdict wins over the host's time check
-  if (loop_fused && c->iters > 0 && c->err == 0 && why != EXIT_RELDELTA) {
-    // the kernels lbfgs_update! rides on leave `dirt *= α` (src/lbfgs.jl:142) to a copy dirt ← s_latest, made when
-    // something looks at dirt (ensure_dirt)
-    s->dirt_from = c->latest - 1;
-  } else if (c->iters == 0 && c->err == 0) {
-    s->dirt_from = dirt_was_from;   // not one iteration ran: dirt is what it was
-  }
+  if (c->iters == 0 && c->err == 0) s->dirt_from = e.dirt_was_from;   // not one iteration ran: dirt is what it was
   if (dbg)
     fprintf(stderr, "[sdplr_hip] inner_loop: %d batches (%s), host enqueue %.3f ms, host wait %.3f ms, iters %lld\n",
             n_batches, use_graph ? "graph" : "eager", 1e3 * t_enq, 1e3 * t_wait, (long long)c->iters);
-  // G was rewritten by g! after the last update when the loop left through the relative-decrease
-  // exit (no lbfgs_update!, src/sdplr.jl:239-241): the dots with G are stale then.
-  s->sg_stale = (why == EXIT_RELDELTA);
-  s->ynext_pending = (why == EXIT_RELDELTA) && s->h > 0;
-  if (c->err == SDPLR_ERR_NOT_DESCENT) {
-    const int latest_ = c->latest;
-    c->err = 0; c->done = 0;
-    (void)push(s);
-    // lbfgs_dir! ran, the step did not: on a ring the direction lies at position ring_k (unc = 2: k_ring_materialize)
-    if (s->ring_now) { s->st_ring_loops++; s->ring_unc = 2; }
-    s->P_age += c->iters;
-    s->G_age = s->pdrop_now ? s->G_age + c->iters : 0;
-    if ((rc = park_ynext_after_not_descent(s, latest_))) return rc;
-    return fail(s, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
-  }
-  s->st_iters += c->iters;
-  s->P_age += c->iters;
-  s->G_age = s->pdrop_now ? s->G_age + c->iters : 0;   // (the P-based kernels form G from P and y at every step)
-  if (s->pdrop_now) s->st_pdrop++;
-  if (s->ring_now) s->st_ring_loops++;
-  s->G_consistent = true;                              // g! has run at the loop's last point
+  if ((rc = loop_leave(s, rt, LoopOutcome{c->iters, why, c->err, c->latest}))) return rc;
   *Lio = c->L; *gnio = c->gnorm; *pnio = c->pvnorm;
   if (last_alpha) *last_alpha = c->alpha;
   if (iters) *iters = c->iters;
   if (exit_reason) *exit_reason = why;
   return sync_check(s);
+}
+int32_t sdplr_hip_inner_loop(S* s, double normC, double normb, int32_t grel, int32_t prel, int32_t use_armijo,
+                             double cur_gtol, double fprec_eps, int64_t max_local_iters, double time_budget_s,
+                             double* Lio, double* gnio, double* pnio, double* last_alpha, int64_t* iters,
+                             int32_t* exit_reason) {
+  return inner_loop_impl(s, loop_params(normC, normb, grel, prel, use_armijo, 0.0, cur_gtol, fprec_eps, max_local_iters, time_budget_s,
+                                        Lio, gnio, pnio),
+                         Lio, gnio, pnio, last_alpha, iters, exit_reason, false);
 }
 
 // One major iteration's device work as ONE call: [λ update (src/sdplr.jl:358-362)] → σ → lbfgs_clear! (:384) → fg! (:389)
@@ -4134,23 +4145,19 @@ int32_t sdplr_hip_major_iteration(S* s, double normC, double normb, int32_t grel
                                   double* last_alpha, int64_t* iters, int32_t* exit_reason) {
   if (!s) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "null handle");
   if (!L || !gn || !pn || max_local_iters < 1) return fail(s, SDPLR_ERR_INVALID_ARG, "major_iteration: bad args");
+  const LoopParams p = loop_params(normC, normb, grel, prel, use_armijo, sigma, cur_gtol, fprec_eps, max_local_iters, time_budget_s, L, gn, pn);
   if (update_lambda == SDPLR_MAJOR_RESUME)   // the while loop continues where a capped call left it: ℒ and the norms are in/out
-    return inner_loop_impl(s, normC, normb, grel, prel, use_armijo, cur_gtol, fprec_eps, max_local_iters, time_budget_s, L, gn, pn,
-                           last_alpha, iters, exit_reason, true);
-  bool resident = false;
+    return inner_loop_impl(s, p, L, gn, pn, last_alpha, iters, exit_reason, true);
   {
     ApiShared api_guard(dev_of(s));
     { const int rc_r = ring_drop_for_clear(s); if (rc_r) return rc_r; }   // (lbfgs_clear! follows on every route)
     NEED_FINAL_RW(s);
-    resident = rs_loop_applies(s, use_armijo) && rs_fg_applies(s);
-    if (resident) {
+    const LoopRoute rt = choose_loop_route(s, use_armijo, false, false, true);
+    if (rt.kind == LOOP_RESIDENT) {
       // var.σ[], the loop's parameters and its counters ride the launch's arguments (the kernel writes them into its copy
       // of the control block after the λ update has read the σ it found there): no pull / push of the block in front
-      RsLoopIn in{};
-      in.sigma = sigma; in.gtol = cur_gtol; in.fprec = fprec_eps; in.normC = normC; in.normb = normb;
-      in.grel = grel; in.prel = prel; in.max_iters = max_local_iters;
       s->sg_stale = s->ynext_pending = false;   // (cleared history: see sdplr_hip_lbfgs_clear)
-      return run_resident_loop(s, time_budget_s, update_lambda != 0, true, L, gn, pn, last_alpha, iters, exit_reason, &in);
+      return run_resident_loop(s, p, rt, update_lambda != 0, L, gn, pn, last_alpha, iters, exit_reason);
     }
   }
   int32_t rc;
@@ -4707,7 +4714,8 @@ std::vector<long long> edge_group_key(const S* s) {
 }
 struct GroupMember {
   sdplr_hip_major_item* q;
-  int dirt_was_from;
+  LoopRoute rt;
+  LoopEntry e;
 };
 // The inner while loops (src/sdplr.jl:190-278) of `mem` — ≥ 2 instances of one key, each with ℒ, ‖∇ℒ‖, ‖pv‖ of its fg! in
 // its item — as shared launches on the first member's stream.  Entry and exit per member are those of inner_loop_impl on
@@ -4719,23 +4727,11 @@ int run_edge_group(std::vector<GroupMember>& mem) {
   for (GroupMember& g : mem) {      // ---- entry, per member
     sdplr_hip_major_item& q = *g.q;
     S* sk = q.s;
-    const bool hc_was_valid = sk->hc_valid;
-    g.dirt_was_from = sk->dirt_from;
-    sk->dirt_from = -1;             // (the direction kernel overwrites dirt: a pending dirt ← s_latest is dropped)
-    sk->hc_valid = false;
-    sk->G_consistent = false;
-    const bool gram_work = sk->gram_dirty || sk->ynext_pending || sk->sg_stale;
-    ensure_gram(sk);
-    sk->hc_valid = hc_was_valid && !gram_work;
-    int rc = pull_if_stale(sk);
+    g.rt = choose_loop_route(sk, q.use_armijo, false, false, false);   // (LOOP_EDGE: edge_group_applies)
+    g.rt.shared = true;
+    int rc = loop_enter(sk, false, &g.e);
     if (rc) return rc;
-    sk->hc_valid = false;
-    DevCtrl* c = sk->hc;
-    c->done = 0; c->exit_reason = 0; c->err = 0; c->use_armijo = 0;
-    c->iters = 0; c->max_iters = q.max_local_iters; c->reldelta_exit = 0; c->norms_pending = 0; c->pv2_extra = 0.0;
-    c->cur_gtol = q.cur_gtol; c->fprec_eps = q.fprec_eps; c->normC = q.normC; c->normb = q.normb;
-    c->grel = q.gtol_relative; c->prel = q.ptol_relative;
-    c->L = q.lagrangian; c->gnorm = q.grad_norm; c->pvnorm = q.primal_vio_norm; c->alpha = 0.0; c->alpha_max = 1.0;
+    loop_params_to_ctrl(sk->hc, loop_params(q));
     if ((rc = push(sk))) return rc;   // (waits: the shared launches run on another stream)
     sk->S_stale = true; sk->S_from_y = true;
   }
@@ -4842,23 +4838,12 @@ int run_edge_group(std::vector<GroupMember>& mem) {
     enq_boundary(sk, 0, 1, 0, 0);
     if ((rc = pull(sk))) { q.status = rc; if (!first_rc) first_rc = rc; continue; }
     DevCtrl* c = sk->hc;
-    int why = c->done ? c->exit_reason : (timed_out ? EXIT_TIME : -1);
-    if (c->iters > 0 && c->err == 0 && why != EXIT_RELDELTA) sk->dirt_from = c->latest - 1;
-    else if (c->iters == 0) sk->dirt_from = g.dirt_was_from;
-    sk->sg_stale = (why == EXIT_RELDELTA);
-    sk->ynext_pending = (why == EXIT_RELDELTA) && sk->h > 0;
-    if (c->err == SDPLR_ERR_NOT_DESCENT) {
-      c->err = 0; c->done = 0;
-      (void)push(sk);
-      q.status = fail(sk, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
+    const int why = c->done ? c->exit_reason : (timed_out ? EXIT_TIME : -1);
+    if (c->iters == 0 && c->err == 0) sk->dirt_from = g.e.dirt_was_from;   // not one iteration ran: dirt is what it was
+    if ((q.status = loop_leave(sk, g.rt, LoopOutcome{c->iters, why, c->err, c->latest}))) {
       if (!first_rc) first_rc = q.status;
       continue;
     }
-    sk->st_iters += c->iters;
-    sk->P_age += c->iters;
-    sk->G_age = 0;
-    sk->G_consistent = true;
-    sk->st_grp_loops++;
     q.lagrangian = c->L; q.grad_norm = c->gnorm; q.primal_vio_norm = c->pvnorm; q.last_alpha = c->alpha; q.obj = c->obj;
     q.iters_done = c->iters; q.exit_reason = why;
     q.status = SDPLR_OK;
@@ -4958,16 +4943,19 @@ int32_t sdplr_hip_batch_major_iteration(int32_t count, sdplr_hip_major_item* it)
     ApiShared api_guard(dev);
     std::map<ShapeKey, std::vector<int>> groups;
     std::vector<char> was_cons(count, 0);
+    std::vector<LoopRoute> routes(count);   // (LOOP_GENERIC until chosen)
     for (int i = 0; i < count; i++) {
       S* s = it[i].s;
       const bool was_consistent = s && s->G_consistent;
       was_cons[i] = was_consistent ? 1 : 0;
       if (s) s->G_consistent = false;
       const bool resume = it[i].update_lambda == SDPLR_MAJOR_RESUME;
-      // (fg! runs in the prologue: G is fresh, the P-less loop applies; a resumed loop takes the kernel it was capped in)
-      const bool pd = s && rs_can_drop_P(s) && (!resume || (was_consistent && s->pdrop_now));
-      if (s && s->finalized && it[i].max_local_iters >= 1 && rs_loop_applies(s, it[i].use_armijo) && rs_fg_applies(s)) {
-        groups[{(pd ? 1 : 0) + 10 * (pd ? rs_team_w(s) : 1), rs_vec(s)}].push_back(i);   // (kernel, team size | shape)
+      // (fg! runs in the prologue of every loop that is not a resumed one)
+      LoopRoute& rt = routes[i];
+      if (s && s->finalized && it[i].max_local_iters >= 1) rt = choose_loop_route(s, it[i].use_armijo, resume, was_consistent, !resume);
+      rt.shared = true;
+      if (rt.kind == LOOP_RESIDENT) {
+        groups[{(rt.pdrop ? 1 : 0) + 10 * rt.team_w, rs_vec(s)}].push_back(i);   // (kernel, team size | shape)
       } else {
         if (s) s->G_consistent = was_consistent;   // (the single-instance entry point looks at it itself)
         if (edge_group_applies(s, it[i])) egroups[edge_group_key(s)].push_back(i);
@@ -5021,12 +5009,9 @@ int32_t sdplr_hip_batch_major_iteration(int32_t count, sdplr_hip_major_item* it)
             if (!rc_pre) { rc_pre = rc_k; if (sk != s) s->err = sk->err; }
           }
           if (!resume) sk->sg_stale = sk->ynext_pending = false;   // (cleared history: see sdplr_hip_lbfgs_clear)
-          RsLoopArgs a = resume ? rs_loop_args(sk, q.time_budget_s, !sk->P_valid, false, false)
-                                : rs_loop_args(sk, q.time_budget_s, true, q.update_lambda != 0, true);
-          RsLoopIn in{};
-          in.sigma = q.sigma; in.gtol = q.cur_gtol; in.fprec = q.fprec_eps; in.normC = q.normC; in.normb = q.normb;
-          in.grel = q.gtol_relative; in.prel = q.ptol_relative; in.max_iters = q.max_local_iters;
-          rs_loop_set_in(a, in);
+          const LoopRoute& rt = routes[idx[lo + k]];
+          RsLoopArgs a = rs_loop_args(sk, q.time_budget_s, rt.refresh_P, rt.prologue && q.update_lambda != 0, rt.prologue);
+          rs_loop_set_in(a, loop_params(q));
           a.out = reinterpret_cast<double*>(bb.dev + res_off) + 8 * k;
           if (g_w > 1) {
             a.team_w = g_w;
@@ -5058,28 +5043,7 @@ int32_t sdplr_hip_batch_major_iteration(int32_t count, sdplr_hip_major_item* it)
             single.push_back(idx[lo + k]);
             continue;
           }
-          if (err == SDPLR_ERR_TEAM_TIMEOUT) {
-            q.status = fail(sk, SDPLR_ERR_HIP, "resident loop: a team member never arrived at a barrier (the grid was not co-resident)");
-            continue;
-          }
-          // (the bookkeeping of run_resident_loop)
-          const bool pd = g_pd, resumed = q.update_lambda == SDPLR_MAJOR_RESUME;
-          sk->pdrop_now = pd;
-          if (pd) sk->st_pdrop++;
-          sk->P_valid = !pd; sk->P_age = (resumed ? sk->P_age : 0) + iters; sk->S_stale = true; sk->S_from_y = true;
-          sk->G_consistent = true; sk->G_age = pd ? (resumed ? sk->G_age : 0) + iters : 0;
-          if (!resumed) { sk->st_rs_fg++; sk->gram_dirty = false; }
-          sk->st_rs_loops++; sk->st_rs_shared++;
-          sk->sg_stale = (why == EXIT_RELDELTA);
-          sk->ynext_pending = (why == EXIT_RELDELTA) && sk->h > 0;
-          if (err == SDPLR_ERR_NOT_DESCENT) {
-            int r2 = pull(sk);
-            if (!r2) { sk->hc->err = 0; sk->hc->done = 0; r2 = push(sk); }
-            if (!r2) r2 = park_ynext_after_not_descent(sk, sk->hc->latest);
-            q.status = r2 ? r2 : fail(sk, SDPLR_ERR_NOT_DESCENT, "Error: cubic[1] should be less than 0.");
-            continue;
-          }
-          sk->st_iters += iters;
+          if ((q.status = loop_leave(sk, routes[idx[lo + k]], LoopOutcome{iters, why, err, -1}))) continue;
           q.lagrangian = o[0]; q.grad_norm = o[1]; q.primal_vio_norm = o[2]; q.last_alpha = o[3]; q.obj = o[4];
           q.iters_done = iters; q.exit_reason = why;
         }
@@ -5107,7 +5071,7 @@ int32_t sdplr_hip_batch_major_iteration(int32_t count, sdplr_hip_major_item* it)
       sdplr_hip_major_item& q = it[i];
       if (q.status != SDPLR_ERR_UNSERVED) continue;               // (its prologue failed)
       if (!(q.grad_norm > q.cur_gtol)) { q.status = SDPLR_OK; continue; }   // src/sdplr.jl:190: the loop is not entered
-      live.push_back(GroupMember{&q, -1});
+      live.push_back(GroupMember{&q, LoopRoute{}, LoopEntry{}});
     }
     if (live.size() >= 2) {
       ApiShared api_guard(dev);

@@ -8,8 +8,11 @@ B  one handle moved between the multi-launch route (history in ring form, k_dens
    the resident group launch of batch_major_iteration, in production mode (no SDPLR_HIP_FORCE_GRAPH).
 C  G carried forward by G_new = G_old + 2(αW + d∘R − d′∘R′) (k_sparse.h) for 512 and 1000 iterations in one call, against a
    gradient evaluated above FP64 (helpers.hp_gradient); the second run ends in the stalled regime (α = 0, s = y = 0).
+D  the refresh by age (SDPLR_HIP_P_REFRESH_ITERS) falls due between calls of their own and never in a resumed loop.
 
 The oracle halves of A and C are pinned without a GPU in test_oracle_endtoend.py."""
+import sys
+
 import numpy as np
 import pytest
 
@@ -430,3 +433,79 @@ def test_loop_in_the_stalled_regime(hip_abi, oracle_abi, monkeypatch):
     same_state(ring["state"], stored["state"])
     _check_carry(ring, prob, K_moving)
     _check_carry(stored, prob, K_moving)
+
+
+# ---- D: a refresh by age between calls, and none in a resumed loop --------------------------------------------------------
+REFRESH_AGE, CAP = 4, 3
+
+
+def _refresh_and_resume_child():
+    """Runs in a process of its own (SDPLR_HIP_P_REFRESH_ITERS is read once per process): prints one JSON line with the
+    counters of the three handles per instance, after asserting cap + resume ≡ uncapped itself (arrays stay here)."""
+    import json
+
+    from sdplrplus_jl_amd import load_hip
+    hip_abi = load_hip()
+    report, lc = {}, long_carry_instance()
+    for name, (data, r, seed) in (("not_descent", not_descent_instance("launches")), ("long_carry", lc[:1] + lc[4:])):
+        nC, nb = data.normC(), float(np.linalg.norm(data.b))
+        major = lambda s_, upd, k, st=(): s_.major_iteration(nC, nb, True, True, False, upd, 2.0, 0.0, -1e300, k, 0.0, *st[:3])
+        # three calls of their own: G is 2·CAP ≥ REFRESH_AGE iterations old in front of the third
+        a, _ = make_solver(hip_abi, data, r, seed=seed, h=H)
+        st, per_call = a.fg(nC, nb), []
+        for _ in range(3):
+            before = a.stats()
+            st = loop(a, nC, nb, CAP, st)
+            assert st[4] == CAP and st[5] == 2, st
+            per_call.append(delta(a.stats(), before))
+        a.close()
+        # one loop of 3·CAP iterations in three pieces, and in one
+        b, _ = make_solver(hip_abi, data, r, seed=seed, h=H)
+        out_b, pieces = major(b, 0, CAP), []
+        for _ in range(2):
+            assert out_b[4] == CAP and out_b[5] == 2, out_b
+            before = b.stats()
+            out_b = major(b, cabi.MAJOR_RESUME, CAP, out_b)
+            pieces.append(delta(b.stats(), before))
+        stats_b = b.stats()
+        c, _ = make_solver(hip_abi, data, r, seed=seed, h=H)
+        out_c = major(c, 0, 3 * CAP)
+        stats_c = c.stats()
+        print(name, "resumed:", out_b, "uncapped:", out_c, file=sys.stderr)
+        assert out_b[:4] == out_c[:4] and out_b[4] == CAP and out_c[4] == 3 * CAP and out_b[5] == out_c[5] == 2
+        same_state(history_state(b, H), history_state(c, H))
+        b.close(); c.close()
+        report[name] = dict(calls=per_call, pieces=pieces, resumed=stats_b, uncapped=stats_c)
+    print(json.dumps(report))
+
+
+def test_refresh_by_age_between_calls_and_none_in_a_resumed_loop():
+    """SDPLR_HIP_P_REFRESH_ITERS = 4 on the fast2 route (P-less step kernel, history in ring form), two instances.  Three calls
+    of 3 iterations: in front of the third the carried G is 6 iterations old, so it is formed from scratch — at its own place,
+    which ends the ring the first two calls shared (one materialisation), and the call enters a ring of its own.  The same 9
+    iterations as one major_iteration capped at 3 and two SDPLR_MAJOR_RESUME calls of 3: a resumed loop takes the kernel the
+    capped call took and refreshes nothing by age — one ring throughout, no materialisation — and is one uncapped call of 9
+    bit for bit (asserted in the child, where the arrays are)."""
+    import json
+    import os
+    import subprocess
+    tests = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, SDPLR_HIP_P_REFRESH_ITERS=str(REFRESH_AGE), SDPLR_HIP_FORCE_GRAPH="1")
+    for k in ("SDPLR_HIP_NO_RING", "SDPLR_HIP_NO_GRAPH", "SDPLR_HIP_NO_RESIDENT", "SDPLR_HIP_NO_PDROP"):
+        env.pop(k, None)
+    code = (f"import sys; sys.path[:0] = [{tests!r}, {os.path.dirname(tests)!r}]; "
+            "import test_gpu_handover as t; t._refresh_and_resume_child()")
+    p = subprocess.run([sys.executable, "-s", "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    print(p.stdout, p.stderr[-3000:])
+    assert p.returncode == 0, p.stderr[-3000:]
+    report = json.loads(p.stdout.strip().splitlines()[-1])
+    assert set(report) == {"not_descent", "long_carry"}
+    for name, rep in report.items():
+        for i, d in enumerate(rep["calls"]):      # every call P-less and on a ring; only the third one due for its refresh
+            assert d["p_less_loops"] == 1 and d["ring_history_loops"] == 1 and d["resident_loops"] == 0, (name, i, d)
+            assert d["ring_materializations"] == (1 if i == 2 else 0), (name, i, d)
+        for i, d in enumerate(rep["pieces"]):     # the resumed pieces: the capped call's kernel, its ring kept
+            assert d["p_less_loops"] == 1 and d["ring_history_loops"] == 1 and d["ring_materializations"] == 0, (name, i, d)
+        assert rep["resumed"]["p_less_loops"] == 3 and rep["resumed"]["ring_history_loops"] == 3, (name, rep["resumed"])
+        assert rep["resumed"]["ring_materializations"] == 0 and rep["uncapped"]["ring_materializations"] == 0, name
+        assert rep["uncapped"]["p_less_loops"] == 1 and rep["uncapped"]["ring_history_loops"] == 1, (name, rep["uncapped"])
