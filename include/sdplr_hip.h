@@ -347,8 +347,11 @@ int32_t sdplr_hip_factor_dot(sdplr_hip_solver* s, int32_t slot_a, int32_t slot_b
  * path (one launch per kernel of the while body for the whole group, sdplr_hip_batch_major_iteration), out[14] the
  * inner loops (calls) that ran on the RING form of the L-BFGS history (lbfgshis.vecs[j].s / .y of src/lbfgs.jl:4-12
  * kept as (α_j, dir_j) and (G_j, G_{j+1}) inside the loop: the same values, two stores per iteration less), out[15]
- * the times that form was turned back into stored s_j, y_j because something outside the loop looked.  Writes
- * min(cap, 16) entries, *n_written says how many.                                                               */
+ * the times that form was turned back into stored s_j, y_j because something outside the loop looked, out[16] and
+ * out[17] the residency windows of the last ring iteration enqueued, in rows (not counters): the last rows whose history
+ * the step kernel loaded with plain instead of non-temporal loads, and the lowest rows the direction kernel loaded so
+ * (both sized from SDPLR_HIP_LLC_WINDOW_KB, a byte budget in KiB read when the handle is created; 0 = no window).  Writes
+ * min(cap, 18) entries, *n_written says how many.                                                               */
 int32_t sdplr_hip_get_stats(const sdplr_hip_solver* s, int64_t* out, int32_t cap, int32_t* n_written);
 
 /* ---- per-kernel device timing (hipEvent pairs on the handle's stream) ------------------------ */

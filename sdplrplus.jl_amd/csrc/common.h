@@ -19,6 +19,9 @@
 #define SDPLR_MAXNB 4096       // largest grid of a partial-producing kernel (width of a partial slot)
 #define SDPLR_NSLOT 160        // reduction slots in the partials buffer
 #define SDPLR_LRMAX 8          // low-rank columns handled per register pass
+#ifndef SDPLR_LLC_WINDOW_DEFAULT_KB
+#define SDPLR_LLC_WINDOW_DEFAULT_KB (256LL << 10)   // byte budget of the ring kernels' residency windows, in KiB (SDPLR_HIP_LLC_WINDOW_KB)
+#endif
 
 // exit reasons of the inner loop (include/sdplr_hip.h, sdplr_hip_inner_loop)
 #define EXIT_GTOL 0

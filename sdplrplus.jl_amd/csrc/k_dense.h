@@ -15,6 +15,7 @@
 // inside it the singleton loops keep them as the arrays they are functions of ("ring form" below): the same values, formed
 // on the fly.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 struct FactorArena {
@@ -586,9 +587,16 @@ k_lbfgs_dir(const DevCtrl* __restrict__ c, FactorArena A, long long N, int h, in
 // ring.  2h + 1 loads per element, as the stored form.  The steepest-descent fallback (decided by the seam kernel from the
 // Gram data) writes −G and leaves G alone: the flip G ← −G of src/sdplr.jl:203 is undone by the step kernel's y_j = G_new −
 // G_old in the stored form, and here nothing else reads G in between.  N even.
+// The sweep runs from the LAST element pair down: the step kernel before it ascends, so the lines it touched last (G_new,
+// the history of its last rows) are met first, while they may still sit in the Infinity Cache; the kernel is elementwise,
+// the order changes no value.  NTH: history loads non-temporal, except in the trips that lie wholly below pair `plain_below`
+// (the residency window of the step kernel that follows and starts at row 0: those lines should allocate); the choice is
+// uniform per trip.  NTH = false: plain loads everywhere.  descend = 0: the ascending sweep, pair i in place of N/2 − 1 − i (rows
+// wider than 256 bytes, where the descending one measured slower: DESIGN §12; the host then passes plain_below = 0).
 template <int HM, bool NTH>
 __global__ void __launch_bounds__(SDPLR_NT)
-k_lbfgs_dir_ring(const DevCtrl* __restrict__ c, FactorArena A, long long N, int h, int check_done) {
+k_lbfgs_dir_ring(const DevCtrl* __restrict__ c, FactorArena A, long long N, int h, int check_done, long long plain_below,
+                 int descend) {
   const int dn = check_done ? c->done : 0;
   const int latest = c->latest, rk = c->ring_k, rn = c->ring_n, j0 = c->ring_j0, fb = c->fallback;
   double ca[HM], cg[HM], ra[HM];
@@ -628,12 +636,17 @@ k_lbfgs_dir_ring(const DevCtrl* __restrict__ c, FactorArena A, long long N, int 
   double* dir = ring_D(A, rk, j0);
   const long long N2 = N >> 1;
   const long long stride = (long long)gridDim.x * SDPLR_NT;
-  for (long long i = (long long)blockIdx.x * SDPLR_NT + threadIdx.x; i < N2; i += stride) {
+  const long long first = (long long)blockIdx.x * SDPLR_NT + threadIdx.x;
+  // one trip: pairs N2 − 1 − base − [0, stride) (ascending: base + [0, stride)); NT: the history non-temporal; GNT: G_new non-temporal
+  auto trip = [&](long long base, auto nt, auto gnt) __attribute__((always_inline)) {
+    constexpr bool NT = decltype(nt)::value, GNT = decltype(gnt)::value;
+    if (base + first >= N2) return;
+    const long long i = descend ? N2 - 1 - (base + first) : base + first;
     double2 gv[HM + 1], dv[HM];
-    gv[0] = ldnt2(gp[0], i);
+    gv[0] = GNT ? ldnt2(gp[0], i) : reinterpret_cast<const double2*>(gp[0])[i];
 #pragma unroll
     for (int k = 0; k < HM; k++) {
-      if constexpr (NTH) {
+      if constexpr (NT) {
         gv[k + 1] = ldnt2(gp[k + 1], i);
         dv[k] = ldnt2(dp[k], i);
       } else {
@@ -663,6 +676,15 @@ k_lbfgs_dir_ring(const DevCtrl* __restrict__ c, FactorArena A, long long N, int 
       d.y = -gv[0].y;
     }
     reinterpret_cast<double2*>(dir)[i] = d;
+  };
+  using std::true_type;
+  using std::false_type;
+  long long base = 0;
+  if constexpr (NTH) {   // the trips that reach above the window, then the ones inside it: two loops, one register set each
+    for (; base < N2 && N2 - 1 - base >= plain_below; base += stride) trip(base, true_type{}, true_type{});
+    for (; base < N2; base += stride) trip(base, false_type{}, false_type{});
+  } else {
+    for (; base < N2; base += stride) trip(base, false_type{}, true_type{});
   }
 }
 

@@ -1187,7 +1187,7 @@ k_fast_step_ring(int n, int m, DevFast ff, double* __restrict__ R, const double*
                  double* __restrict__ yvec, const double* __restrict__ lam, const double* __restrict__ lam_ub,
                  double* __restrict__ pv_raw, const double* __restrict__ lb, double* __restrict__ pv,
                  const double* __restrict__ A_RD, const double* __restrict__ A_DD, double* __restrict__ partials,
-                 DevCtrl* __restrict__ c, int check_done, FactorArena A, int h, int nb_ls,
+                 DevCtrl* __restrict__ c, int check_done, FactorArena A, int h, int nb_ls, int plain_from,
                  double* __restrict__ P = nullptr, DevLowRank lr = DevLowRank{}, const double* __restrict__ WS = nullptr) {
   static_assert(HMU >= 1, "the ring form rides the fused update");
   __shared__ double sh[2 * (SDPLR_NT / 64)];
@@ -1308,6 +1308,10 @@ k_fast_step_ring(int n, int m, DevFast ff, double* __restrict__ R, const double*
     const long long j0 = tile * TR;
     const int nrows = (int)min((long long)TR, (long long)n - j0);
     if (dn) return;
+    // residency window: the direction kernel that follows sweeps from the last row down, so the history of the tiles from
+    // row plain_from on is loaded plain (it allocates in the Infinity Cache), all earlier rows non-temporally; uniform per
+    // tile (only the one wave whose tiles straddle the boundary runs both variants below)
+    const bool plain = j0 >= plain_from;
     double djl = 0.0, djo = 0.0;     // d_j at the new / the old multipliers
     if (lane < nrows) {
       const long long j = j0 + lane;
@@ -1331,135 +1335,141 @@ k_fast_step_ring(int n, int m, DevFast ff, double* __restrict__ R, const double*
         pv_raw[k] = v;
       }
     }
-    for (int i0 = 0; i0 < nrows; i0 += 2) {
-      vecd<VEC> xx[2], pq[2], dd[2], ww[2], gv[2][HMU], dv[2][HO];
-      double dj[2], dq[2];
-      unsigned off[2];
+    // the rows of the tile, in two inlined variants (history loads non-temporal or plain): one register set each
+    auto rows = [&](auto nt) __attribute__((always_inline)) {
+      constexpr bool NT = decltype(nt)::value;
+      for (int i0 = 0; i0 < nrows; i0 += 2) {
+        vecd<VEC> xx[2], pq[2], dd[2], ww[2], gv[2][HMU], dv[2][HO];
+        double dj[2], dq[2];
+        unsigned off[2];
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int i = min(i0 + u, nrows - 1);                        // (odd tail: row repeated, not stored twice)
-        const long long j = j0 + i;
-        dj[u] = __shfl(djl, i, LPR);
-        dq[u] = __shfl(djo, i, LPR);
-        off[u] = (unsigned)(((unsigned long long)j * (unsigned)r + (unsigned)ch0) * 8ull);
+        for (int u = 0; u < 2; u++) {
+          const int i = min(i0 + u, nrows - 1);                        // (odd tail: row repeated, not stored twice)
+          const long long j = j0 + i;
+          dj[u] = __shfl(djl, i, LPR);
+          dq[u] = __shfl(djo, i, LPR);
+          off[u] = (unsigned)(((unsigned long long)j * (unsigned)r + (unsigned)ch0) * 8ull);
 #pragma unroll
-        for (int q = 0; q < VEC; q++) xx[u].v[q] = pq[u].v[q] = dd[u].v[q] = ww[u].v[q] = 0.0;
+          for (int q = 0; q < VEC; q++) xx[u].v[q] = pq[u].v[q] = dd[u].v[q] = ww[u].v[q] = 0.0;
 #pragma unroll
-        for (int l = 0; l < HMU; l++)
+          for (int l = 0; l < HMU; l++)
 #pragma unroll
-          for (int q = 0; q < VEC; q++) gv[u][l].v[q] = 0.0;
+            for (int q = 0; q < VEC; q++) gv[u][l].v[q] = 0.0;
 #pragma unroll
-        for (int l = 0; l < HO; l++)
+          for (int l = 0; l < HO; l++)
 #pragma unroll
-          for (int q = 0; q < VEC; q++) dv[u][l].v[q] = 0.0;
-        if (ch0 < r) {
-          xx[u] = ldrow<VEC>(rowat(R, off[u]));
-          if (PB) pq[u] = ldrow<VEC>(rowat(P, off[u]));
-          dd[u] = ldrow<VEC>(rowat(D, off[u]));
-          ww[u] = ldrow<VEC>(rowat(W, off[u]));
+            for (int q = 0; q < VEC; q++) dv[u][l].v[q] = 0.0;
+          if (ch0 < r) {
+            xx[u] = ldrow<VEC>(rowat(R, off[u]));
+            if (PB) pq[u] = ldrow<VEC>(rowat(P, off[u]));
+            dd[u] = ldrow<VEC>(rowat(D, off[u]));
+            ww[u] = ldrow<VEC>(rowat(W, off[u]));
 #pragma unroll
-          for (int l = 0; l < HMU; l++) gv[u][l] = ldrow_nt<VEC>(rowat(gp[l], off[u]));
+            for (int l = 0; l < HMU; l++) gv[u][l] = NT ? ldrow_nt<VEC>(rowat(gp[l], off[u])) : ldrow<VEC>(rowat(gp[l], off[u]));
 #pragma unroll
-          for (int l = 0; l < HO; l++) dv[u][l] = ldrow_nt<VEC>(rowat(dp[l], off[u]));
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        if (i0 + u >= nrows) break;
-        if (ch0 >= r) continue;
-        vecd<VEC> x = xx[u];
-        const vecd<VEC> d = dd[u], w = ww[u], go = gv[u][0];
-        vecd<VEC> g;
-        if constexpr (PB) {
-          vecd<VEC> pp = pq[u];
-#pragma unroll
-          for (int q = 0; q < VEC; q++) {
-            x.v[q] += a * d.v[q];
-            pp.v[q] += a * w.v[q];
-            g.v[q] = pp.v[q] * yg + x.v[q] * dj[u];
-          }
-          const long long jrow = j0 + i0 + u;
-          for (int cc = 0; cc < lr.ST; cc++) {
-            const double bb = lr.Bcat[(long long)cc * n + jrow];
-            const vecd<VEC> ws = ldrow<VEC>(WS + (long long)cc * r + ch0);
-#pragma unroll
-            for (int q = 0; q < VEC; q++) g.v[q] += ws.v[q] * bb;
-          }
-#pragma unroll
-          for (int q = 0; q < VEC; q++) {
-            g.v[q] *= 2.0;
-            red[0] += g.v[q] * g.v[q];
-          }
-          strow<VEC>(rowat(P, off[u]), pp);
-        } else {
-          // G_new = G_old + 2·(α·W + d_new∘R_new − d_old∘R_old)   (y_g ≡ 1: A_g is the cost matrix)
-#pragma unroll
-          for (int q = 0; q < VEC; q++) {
-            const double xo = x.v[q];
-            x.v[q] += a * d.v[q];
-            const double t = a * w.v[q] + (x.v[q] * dj[u] - xo * dq[u]);
-            g.v[q] = go.v[q] + 2.0 * t;
-            red[0] += g.v[q] * g.v[q];
+            for (int l = 0; l < HO; l++) dv[u][l] = NT ? ldrow_nt<VEC>(rowat(dp[l], off[u])) : ldrow<VEC>(rowat(dp[l], off[u]));
           }
         }
-#ifdef SDPLR_RING_NT_R
-        strow_nt<VEC>(rowat(R, off[u]), x);
-#else
-        strow<VEC>(rowat(R, off[u]), x);
-#endif
-#ifdef SDPLR_RING_NT_G
-        strow_nt<VEC>(rowat(Gnew, off[u]), g);
-#else
-        strow<VEC>(rowat(Gnew, off[u]), g);
-#endif
-        if (upd) {
-          vecd<VEC> sn, yn;
 #pragma unroll
-          for (int q = 0; q < VEC; q++) {
-            sn.v[q] = a * d.v[q];            // BLAS.scal!(stepsize, dir)  (src/lbfgs.jl:142): kept as (α, D)
-            yn.v[q] = g.v[q] - go.v[q];      // y_j = −G_old + G_new  (:122,145): kept as (G_old, G_new)
-          }
-          double* ac = accl + threadIdx.x;
-#pragma unroll
-          for (int i = 0; i < HO; i++)
-            if (i < nv) {
-              double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
-#pragma unroll
-              for (int q = 0; q < VEC; q++) {
-                const double sl = ra[i] * dv[u][i].v[q];
-                const double yn1 = gv[u][i + 1 < HMU ? i + 1 : i].v[q];
-                const double yl = (i < rn) ? gv[u][i].v[q] - yn1 : yn1;
-                q0 += sn.v[q] * yl;
-                q1 += sl * yn.v[q];
-                q2 += yn.v[q] * yl;
-                q3 += sl * g.v[q];
-                q4 += yl * g.v[q];
-              }
-              const int l = lsl[i];
-              (void)__hip_atomic_fetch_add(ac + (0 * HMU + l) * SDPLR_NT, q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              (void)__hip_atomic_fetch_add(ac + (1 * HMU + l) * SDPLR_NT, q1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              (void)__hip_atomic_fetch_add(ac + (2 * HMU + l) * SDPLR_NT, q2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              (void)__hip_atomic_fetch_add(ac + (3 * HMU + l) * SDPLR_NT, q3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              (void)__hip_atomic_fetch_add(ac + (4 * HMU + l) * SDPLR_NT, q4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-          {   // the new pair with itself
-            double q0 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+        for (int u = 0; u < 2; u++) {
+          if (i0 + u >= nrows) break;
+          if (ch0 >= r) continue;
+          vecd<VEC> x = xx[u];
+          const vecd<VEC> d = dd[u], w = ww[u], go = gv[u][0];
+          vecd<VEC> g;
+          if constexpr (PB) {
+            vecd<VEC> pp = pq[u];
 #pragma unroll
             for (int q = 0; q < VEC; q++) {
-              q0 += sn.v[q] * yn.v[q];
-              q2 += yn.v[q] * yn.v[q];
-              q3 += sn.v[q] * g.v[q];
-              q4 += yn.v[q] * g.v[q];
+              x.v[q] += a * d.v[q];
+              pp.v[q] += a * w.v[q];
+              g.v[q] = pp.v[q] * yg + x.v[q] * dj[u];
             }
-            (void)__hip_atomic_fetch_add(ac + (0 * HMU + jslot) * SDPLR_NT, q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            (void)__hip_atomic_fetch_add(ac + (1 * HMU + jslot) * SDPLR_NT, q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            (void)__hip_atomic_fetch_add(ac + (2 * HMU + jslot) * SDPLR_NT, q2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            (void)__hip_atomic_fetch_add(ac + (3 * HMU + jslot) * SDPLR_NT, q3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            (void)__hip_atomic_fetch_add(ac + (4 * HMU + jslot) * SDPLR_NT, q4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const long long jrow = j0 + i0 + u;
+            for (int cc = 0; cc < lr.ST; cc++) {
+              const double bb = lr.Bcat[(long long)cc * n + jrow];
+              const vecd<VEC> ws = ldrow<VEC>(WS + (long long)cc * r + ch0);
+#pragma unroll
+              for (int q = 0; q < VEC; q++) g.v[q] += ws.v[q] * bb;
+            }
+#pragma unroll
+            for (int q = 0; q < VEC; q++) {
+              g.v[q] *= 2.0;
+              red[0] += g.v[q] * g.v[q];
+            }
+            strow<VEC>(rowat(P, off[u]), pp);
+          } else {
+            // G_new = G_old + 2·(α·W + d_new∘R_new − d_old∘R_old)   (y_g ≡ 1: A_g is the cost matrix)
+#pragma unroll
+            for (int q = 0; q < VEC; q++) {
+              const double xo = x.v[q];
+              x.v[q] += a * d.v[q];
+              const double t = a * w.v[q] + (x.v[q] * dj[u] - xo * dq[u]);
+              g.v[q] = go.v[q] + 2.0 * t;
+              red[0] += g.v[q] * g.v[q];
+            }
+          }
+#ifdef SDPLR_RING_NT_R
+          strow_nt<VEC>(rowat(R, off[u]), x);
+#else
+          strow<VEC>(rowat(R, off[u]), x);
+#endif
+#ifdef SDPLR_RING_NT_G
+          strow_nt<VEC>(rowat(Gnew, off[u]), g);
+#else
+          strow<VEC>(rowat(Gnew, off[u]), g);
+#endif
+          if (upd) {
+            vecd<VEC> sn, yn;
+#pragma unroll
+            for (int q = 0; q < VEC; q++) {
+              sn.v[q] = a * d.v[q];            // BLAS.scal!(stepsize, dir)  (src/lbfgs.jl:142): kept as (α, D)
+              yn.v[q] = g.v[q] - go.v[q];      // y_j = −G_old + G_new  (:122,145): kept as (G_old, G_new)
+            }
+            double* ac = accl + threadIdx.x;
+#pragma unroll
+            for (int i = 0; i < HO; i++)
+              if (i < nv) {
+                double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+#pragma unroll
+                for (int q = 0; q < VEC; q++) {
+                  const double sl = ra[i] * dv[u][i].v[q];
+                  const double yn1 = gv[u][i + 1 < HMU ? i + 1 : i].v[q];
+                  const double yl = (i < rn) ? gv[u][i].v[q] - yn1 : yn1;
+                  q0 += sn.v[q] * yl;
+                  q1 += sl * yn.v[q];
+                  q2 += yn.v[q] * yl;
+                  q3 += sl * g.v[q];
+                  q4 += yl * g.v[q];
+                }
+                const int l = lsl[i];
+                (void)__hip_atomic_fetch_add(ac + (0 * HMU + l) * SDPLR_NT, q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(ac + (1 * HMU + l) * SDPLR_NT, q1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(ac + (2 * HMU + l) * SDPLR_NT, q2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(ac + (3 * HMU + l) * SDPLR_NT, q3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(ac + (4 * HMU + l) * SDPLR_NT, q4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              }
+            {   // the new pair with itself
+              double q0 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+#pragma unroll
+              for (int q = 0; q < VEC; q++) {
+                q0 += sn.v[q] * yn.v[q];
+                q2 += yn.v[q] * yn.v[q];
+                q3 += sn.v[q] * g.v[q];
+                q4 += yn.v[q] * g.v[q];
+              }
+              (void)__hip_atomic_fetch_add(ac + (0 * HMU + jslot) * SDPLR_NT, q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              (void)__hip_atomic_fetch_add(ac + (1 * HMU + jslot) * SDPLR_NT, q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              (void)__hip_atomic_fetch_add(ac + (2 * HMU + jslot) * SDPLR_NT, q2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              (void)__hip_atomic_fetch_add(ac + (3 * HMU + jslot) * SDPLR_NT, q3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              (void)__hip_atomic_fetch_add(ac + (4 * HMU + jslot) * SDPLR_NT, q4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
           }
         }
       }
-    }
+    };
+    if (plain) rows(std::false_type{});
+    else rows(std::true_type{});
   }
   if (dn) return;
   __syncthreads();

@@ -245,6 +245,10 @@ struct sdplr_hip_solver {
   // counters (sdplr_hip_get_stats)
   int64_t st_captures = 0, st_capture_failed = 0, st_capture_skipped = 0, st_graph_batches = 0,
           st_eager_batches = 0, st_lz_graph = 0, st_lz_eager = 0, st_iters = 0, st_rs_loops = 0, st_rs_lz = 0, st_rs_fg = 0, st_rs_shared = 0, st_pdrop = 0, st_grp_loops = 0, st_ring_loops = 0, st_ring_materialized = 0;
+  // residency window of the ring kernels (ring_windows): the budget in bytes (SDPLR_HIP_LLC_WINDOW_KB, read at creation) and
+  // the two windows, in rows, of the last ring iteration enqueued (sdplr_hip_get_stats)
+  long long llc_window_bytes = SDPLR_LLC_WINDOW_DEFAULT_KB << 10;
+  int64_t st_win_dir = 0, st_win_step = 0;
 
   // profiling
   bool prof_on = false;
@@ -1386,7 +1390,7 @@ bool step_can_drop_P(const S* s) {
 // of one chunk, 16-byte pieces, an even number of elements, h ≤ 4
 int tile_shape_lpr(const S* s);
 bool ring_shape_common(const S* s) {
-  return s->fast && s->fast_singleton && step_fuses_update(s) && !s->dot_descent && !s->no_ring && s->VEC == 2 && s->LPR >= 4 &&
+  return s->fast && s->fast_singleton && step_fuses_update(s) && !s->dot_descent && !s->no_ring && s->VEC == 2 &&
          s->r <= (int64_t)s->LPR * s->VEC && (s->N & 1) == 0 && s->use_tile && s->tile_lpr == tile_shape_lpr(s) &&
          !s->tile_panels && s->HM == 4 && !s->lit;
 }
@@ -1417,6 +1421,7 @@ int alloc_factors(S* s) {
   const int G = SDPLR_NT / s->LPR;
   s->nb_dense = blocks_for((s->N + 1) / 2, SDPLR_NT, 1024);
   if (const char* e = getenv("SDPLR_HIP_NB_DENSE")) s->nb_dense = std::max(1, std::min(atoi(e), SDPLR_MAXNB));
+  if (const char* e = getenv("SDPLR_HIP_LLC_WINDOW_KB")) s->llc_window_bytes = std::max(0LL, std::min(atoll(e), 1LL << 40)) << 10;
   s->nb_upd = std::min(s->nb_dense, 256);  // one block per CU streams at full rate; fewer Gram partials for the seam kernel
   if (const char* e = getenv("SDPLR_HIP_NB_UPD")) s->nb_upd = std::max(1, std::min(atoi(e), SDPLR_MAXNB));
   s->nb_sddmm = blocks_for(s->nnzT, G, 8192);
@@ -2462,7 +2467,8 @@ namespace {
   TLV_CASE(8, 2, CALL) TLV_CASE(16, 2, CALL) TLV_CASE(32, 2, CALL) TLV_CASE(64, 2, CALL) {}
 // (the shapes the ring form of the history is built for: ring_shape_ok)
 #define RING_DISPATCH(CALL)                                                                            \
-  LV_CASE(4, 2, CALL) LV_CASE(8, 2, CALL) LV_CASE(16, 2, CALL) LV_CASE(32, 2, CALL) LV_CASE(64, 2, CALL) {}
+  LV_CASE(1, 2, CALL) LV_CASE(2, 2, CALL) LV_CASE(4, 2, CALL) LV_CASE(8, 2, CALL) LV_CASE(16, 2, CALL) LV_CASE(32, 2, CALL) \
+  LV_CASE(64, 2, CALL) {}
 #define HM_DISPATCH(CALL)                                       \
   if (s->HM == 4) { constexpr int HM = 4; CALL; }               \
   else if (s->HM == 8) { constexpr int HM = 8; CALL; }          \
@@ -2684,15 +2690,55 @@ void enq_lbfgs_dir(S* s, int negate, int in_loop, int apply_fallback, bool skip_
   k_descent<<<nb, SDPLR_NT, 0, s->stream>>>(s->ctrl, s->arena, s->N, s->nb_dense, apply_fallback, in_loop, s->partials);
 }
 
+// Residency windows of the ring iteration.  The step kernel ascends over the rows, the direction kernel
+// after it descends (k_dense.h), the gather kernel comes next and the step kernel starts at row 0 again: a line of the
+// history that both kernels touch survives in the Infinity Cache from one to the other while the bytes moved in between
+// fit the budget B.  w_dir: the LAST rows of the step kernel, whose history loads are plain (they allocate) for the
+// direction kernel to find; w_step: the LOWEST rows of the direction kernel, loaded plain for the next step kernel.
+//   w_dir = ⌊B / (step bytes per row + direction bytes per row)⌋,  w_step = ⌊(B − gather bytes) / (the same)⌋,  in [0, n]
+// Per row of r values: step = R, D, W, h G's, h − 1 D's in, R, G out (+ P in and out with PB); direction = h + 1 G's, h D's
+// in, D out; the gather kernel's distinct bytes = R, D in, W out, its lists by SURVEY §8d's count (+ P with PB).
+// An arena that fits the cache as a whole keeps today's hints (direction plain, step non-temporal); B ≥ the arena: plain
+// everywhere; B = 0: no window.  Rows wider than 256 bytes (r > 32) keep the ascending sweep and get no window: at r = 64 and
+// 128 the descending sweep with windows measured 1–2.5 % slower.
+bool ring_descends(const S* s) { return s->r * (long long)sizeof(double) <= 256; }
+bool ring_arena_streams(const S* s) {
+  static const long long nt_above = getenv("SDPLR_HIP_DIR_NT_ABOVE_MB") ? atoll(getenv("SDPLR_HIP_DIR_NT_ABOVE_MB")) << 20 : 200LL << 20;
+  const long long arena_bytes = (long long)(3 + 2 * s->h + (s->fast ? 2 : 0)) * s->arena.stride * (long long)sizeof(double);
+  return arena_bytes > nt_above;
+}
+void ring_windows(S* s, bool pb) {
+  const long long n = s->n, row = s->r * (long long)sizeof(double), h = s->h, B = s->llc_window_bytes;
+  const long long arena_bytes = (long long)(3 + 2 * s->h + (s->fast ? 2 : 0)) * s->arena.stride * (long long)sizeof(double);
+  if (!ring_arena_streams(s)) {
+    s->st_win_dir = 0;
+    s->st_win_step = n;
+    return;
+  }
+  if (!ring_descends(s)) {
+    s->st_win_dir = s->st_win_step = 0;
+    return;
+  }
+  if (B >= arena_bytes) {
+    s->st_win_dir = s->st_win_step = n;
+    return;
+  }
+  const long long per_row = row * ((5 + 2 * h - 1 + (pb ? 2 : 0)) + (2 * h + 2));
+  const long long gather = (3 + (pb ? 1 : 0)) * n * row + 4 * (n + 1) + 12 * (long long)s->nnzS;
+  s->st_win_dir = std::max(0LL, std::min(n, B / per_row));
+  s->st_win_step = std::max(0LL, std::min(n, (B - gather) / per_row));
+}
+
 // the in-loop seam and direction on the ring form of the history (k_dense.h)
 void enq_dir_ring(S* s) {
   enq_boundary(s, 0, 1, 1, 1, 1);
   ProfScope ps(s, "lbfgs_dir");
-  // (history loads non-temporal only when the arena does not fit the 256 MiB Infinity Cache: k_dense.h, NTH)
-  static const long long nt_above = getenv("SDPLR_HIP_DIR_NT_ABOVE_MB") ? atoll(getenv("SDPLR_HIP_DIR_NT_ABOVE_MB")) << 20 : 200LL << 20;
-  const long long arena_bytes = (long long)(3 + 2 * s->h + (s->fast ? 2 : 0)) * s->arena.stride * (long long)sizeof(double);
-  if (arena_bytes > nt_above) k_lbfgs_dir_ring<4, true><<<s->nb_dense, SDPLR_NT, 0, s->stream>>>(s->ctrl, s->arena, s->N, (int)s->h, 1);
-  else k_lbfgs_dir_ring<4, false><<<s->nb_dense, SDPLR_NT, 0, s->stream>>>(s->ctrl, s->arena, s->N, (int)s->h, 1);
+  // (history loads non-temporal only when the arena does not fit the 256 MiB Infinity Cache: k_dense.h, NTH; and then
+  // outside the window of the lowest rows only)
+  ring_windows(s, !s->pdrop_now);
+  const long long plain_below = s->st_win_step * s->r / 2;
+  if (ring_arena_streams(s)) k_lbfgs_dir_ring<4, true><<<s->nb_dense, SDPLR_NT, 0, s->stream>>>(s->ctrl, s->arena, s->N, (int)s->h, 1, plain_below, ring_descends(s) ? 1 : 0);
+  else k_lbfgs_dir_ring<4, false><<<s->nb_dense, SDPLR_NT, 0, s->stream>>>(s->ctrl, s->arena, s->N, (int)s->h, 1, 0, ring_descends(s) ? 1 : 0);
 }
 
 // lbfgs_update!: the pass over the history; its partials are folded by the next seam kernel
@@ -2935,7 +2981,7 @@ void enq_iteration_fast2(S* s) {
       else { TLV_DISPATCH((k_spmm_tile<LPR, VEC, 0><<<s->nb_tile, SDPLR_NT, lds, s->stream>>>(s->tile, (int)s->n, (int)s->m, s->ff, R, D, P, W, (int)s->r, s->lambda, s->pv_raw, s->A_RD, s->A_DD, s->partials, s->ctrl, 1, s->lr, s->lr_part, 0, 1, s->arena))) }
     }
     ProfScope ps(s, "fast_step");
-    RING_DISPATCH((k_fast_step_ring<LPR, VEC, 4><<<s->nb_step, SDPLR_NT, 5 * 4 * SDPLR_NT * sizeof(double), s->stream>>>((int)s->n, (int)s->m, s->ff, R, W, (int)s->r, s->y, s->lambda, s->lambda_ub, s->pv_raw, s->pv_lb, s->pv, s->A_RD, s->A_DD, s->partials, s->ctrl, 1, s->arena, (int)s->h, s->nb_tile)))
+    RING_DISPATCH((k_fast_step_ring<LPR, VEC, 4><<<s->nb_step, SDPLR_NT, 5 * 4 * SDPLR_NT * sizeof(double), s->stream>>>((int)s->n, (int)s->m, s->ff, R, W, (int)s->r, s->y, s->lambda, s->lambda_ub, s->pv_raw, s->pv_lb, s->pv, s->A_RD, s->A_DD, s->partials, s->ctrl, 1, s->arena, (int)s->h, s->nb_tile, (int)(s->n - s->st_win_dir))))
     return;
   }
   const bool ring_pb = s->ring_now;   // … the P-based step kernel on the ring form: the launches below, D found on the ring
@@ -2993,7 +3039,7 @@ void enq_iteration_fast2(S* s) {
     } else if (upd_fused && s->pdrop_now) {   // … P-less: G carried forward from G_old (k_sparse.h, PDROP)
       LV_DISPATCH((k_fast_step2<LPR, VEC, 4, true, true><<<s->nb_step, SDPLR_NT, 5 * 4 * SDPLR_NT * sizeof(double), s->stream>>>((int)s->n, (int)s->m, s->ff, R, D, P, W, G, (int)s->r, s->y, s->lambda, s->lambda_ub, s->pv_raw, s->pv_lb, s->pv, s->A_RD, s->A_DD, s->lr, s->lr_WS, s->partials, s->ctrl, 1, s->arena, (int)s->h, 1)))
     } else if (ring_pb) {   // … the same on the ring form of the history (no s_j, y_j stored)
-      RING_DISPATCH((k_fast_step_ring<LPR, VEC, 4, true><<<s->nb_step, SDPLR_NT, 5 * 4 * SDPLR_NT * sizeof(double), s->stream>>>((int)s->n, (int)s->m, s->ff, R, W, (int)s->r, s->y, s->lambda, s->lambda_ub, s->pv_raw, s->pv_lb, s->pv, s->A_RD, s->A_DD, s->partials, s->ctrl, 1, s->arena, (int)s->h, 0, P, s->lr, s->lr_WS)))
+      RING_DISPATCH((k_fast_step_ring<LPR, VEC, 4, true><<<s->nb_step, SDPLR_NT, 5 * 4 * SDPLR_NT * sizeof(double), s->stream>>>((int)s->n, (int)s->m, s->ff, R, W, (int)s->r, s->y, s->lambda, s->lambda_ub, s->pv_raw, s->pv_lb, s->pv, s->A_RD, s->A_DD, s->partials, s->ctrl, 1, s->arena, (int)s->h, 0, (int)(s->n - s->st_win_dir), P, s->lr, s->lr_WS)))
     } else if (upd_fused) {   // … and lbfgs_update! (:244-246) in the same pass
       LV_DISPATCH((k_fast_step2<LPR, VEC, 4, true><<<s->nb_step, SDPLR_NT, 5 * 4 * SDPLR_NT * sizeof(double), s->stream>>>((int)s->n, (int)s->m, s->ff, R, D, P, W, G, (int)s->r, s->y, s->lambda, s->lambda_ub, s->pv_raw, s->pv_lb, s->pv, s->A_RD, s->A_DD, s->lr, s->lr_WS, s->partials, s->ctrl, 1, s->arena, (int)s->h, s->dot_descent ? 0 : 1)))
     } else {
@@ -3641,10 +3687,11 @@ int32_t sdplr_hip_At_right_device(S* s, const double* x, double* yd, int64_t k) 
 
 int32_t sdplr_hip_get_stats(const S* s, int64_t* out, int32_t cap, int32_t* n_written) {
   if (!s || !out || cap < 0) return SDPLR_ERR_INVALID_ARG;
-  const int64_t v[16] = {s->st_captures, s->st_capture_failed, s->st_capture_skipped, s->st_graph_batches,
+  const int64_t v[18] = {s->st_captures, s->st_capture_failed, s->st_capture_skipped, s->st_graph_batches,
                          s->st_eager_batches, s->st_lz_graph, s->st_lz_eager, s->st_iters, s->st_rs_loops, s->st_rs_lz, s->st_rs_fg,
-                         s->st_rs_shared, s->st_pdrop, s->st_grp_loops, s->st_ring_loops, s->st_ring_materialized};
-  const int32_t k = std::min<int32_t>(cap, 16);
+                         s->st_rs_shared, s->st_pdrop, s->st_grp_loops, s->st_ring_loops, s->st_ring_materialized,
+                         s->st_win_dir, s->st_win_step};
+  const int32_t k = std::min<int32_t>(cap, 18);
   for (int32_t i = 0; i < k; i++) out[i] = v[i];
   if (n_written) *n_written = k;
   return SDPLR_OK;
