@@ -984,3 +984,201 @@ def check_linesearch_call(base: dict, st: dict, solver) -> dict:
     out["obj_is_last"] = bool(solver.obj == pv[m])
     out["pv_is_raw"] = bool(np.array_equal(solver.primal_vio, np.maximum(pv[:m], solver.primal_vio_lb)))
     return out
+
+
+# ---- f!, g!, 𝒜 and 𝒜ᵀ above FP64 from the matrices' own entries (tests/test_fg_reference.py, tests/test_gpu_fg_operators.py) ----
+def _hp_matmul(A, B):
+    """A·B of two double matrices above FP64 (np.longdouble; where that is a double, every entry through _hp_dot)."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if WIDE:
+        Al, Bl = A.astype(LD), B.astype(LD)
+        if A.shape[0] <= 16:       # a few long rows (Bᵀ·R of a low-rank term): one vectorised pass per row
+            return np.stack([np.sum(Al[i][:, None] * Bl, axis=0) for i in range(A.shape[0])]).reshape(A.shape[0], B.shape[1])
+        if A.shape[1] <= 16:       # a few columns (B·(Bᵀ R)): a sum of outer products
+            return sum((Al[:, k][:, None] * Bl[k][None, :] for k in range(A.shape[1])), np.zeros((A.shape[0], B.shape[1]), dtype=LD))
+        return Al @ Bl
+    return np.array([[_hp_dot(A[i], B[:, j]) for j in range(B.shape[1])] for i in range(A.shape[0])]).reshape(A.shape[0], B.shape[1])
+
+
+def _hp_rowdots(U, V, I, J):
+    """⟨U_I[k], V_J[k]⟩ for every k above FP64."""
+    if WIDE:
+        return np.sum(_ld(U)[I] * _ld(V)[J], axis=1)
+    return np.array([_hp_dot(U[i], V[j]) for i, j in zip(I, J)], dtype=np.float64).reshape(len(I))
+
+
+def _hp_segsum(w, x, owner, size):
+    """out[owner[k]] += w[k]·x[k] above FP64 (w double, x in the wide type; with doubles: math.fsum of exact products)."""
+    if WIDE:
+        out = np.zeros(size, dtype=LD)
+        np.add.at(out, owner, _ld(w) * x)
+        return out
+    import math
+    out = np.zeros(size)
+    order = np.argsort(owner, kind="stable")
+    cuts = np.searchsorted(owner[order], np.arange(size + 1))
+    for k in range(size):
+        sel = order[cuts[k]:cuts[k + 1]]
+        if sel.size:
+            out[k] = math.fsum(_two_prod_terms(np.asarray(w, dtype=np.float64)[sel], np.asarray(x, dtype=np.float64)[sel]))
+    return out
+
+
+def split_matrices(C, As):
+    """The matrices' own entries: the sparse ones concatenated as (I, J, V, owner) — owner the index into the (m + 1)-vectors,
+    the cost matrix last; entries in stored order, duplicates kept — and the low-rank ones as (owner, D, B)."""
+    from sdplrplus_jl_amd.structs import _entries_findnz_order
+    Is, Js, Vs, Os, lows = [], [], [], [], []
+    for gid, M in enumerate(list(As) + [C]):
+        if isinstance(M, sj.SymLowRankMatrix):
+            lows.append((gid, M.D, M.B))
+            continue
+        I, J, V = _entries_findnz_order(M)
+        Is.append(I); Js.append(J); Vs.append(V); Os.append(np.full(len(I), gid, dtype=np.int64))
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dtype=dt)
+    return (cat(Is, np.int64), cat(Js, np.int64), cat(Vs, np.float64), cat(Os, np.int64)), lows
+
+
+def A_pair_hp(C, As, U, V) -> dict:
+    """q[i] = ⟨Aᵢ, (UVᵀ + VUᵀ)/2⟩ for every matrix (cost last) above FP64, entry by entry (a low-rank one as Σ_c d_c⟨Bᵀ_cU,
+    Bᵀ_cV⟩), never an n×n array; mag[i] the sum of the magnitudes of its elementary products, Σ|a_jk|(⟨|U_j|,|V_k|⟩ +
+    ⟨|V_j|,|U_k|⟩)/2; depth[i] the roundings an FP64 evaluation makes on the way to one output in ANY summation order:
+    k·r products and their sum per stored upper-triangular entry (k = 1 for U = V, else 2), the Lᵢ entries' sum, and four for
+    the weights, the halving and the last store → k·r + Lᵢ + 4; a low-rank matrix k·n·s·r + r + 4."""
+    U64, V64 = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    same = U64 is V64 or np.array_equal(U64, V64)
+    k = 1 if same else 2
+    n, r = U64.shape
+    (I, J, W, own), lows = split_matrices(C, As)
+    M = len(As) + 1
+    aU, aV = np.abs(U64), np.abs(V64)
+    if same:
+        d, dm = _hp_rowdots(U64, U64, I, J), _hp_rowdots(aU, aU, I, J)
+    else:
+        d = (_hp_rowdots(U64, V64, I, J) + _hp_rowdots(V64, U64, I, J)) / 2
+        dm = (_hp_rowdots(aU, aV, I, J) + _hp_rowdots(aV, aU, I, J)) / 2
+    q, mag = _hp_segsum(W, d, own, M), _hp_segsum(np.abs(W), dm, own, M)
+    depth = np.zeros(M)
+    np.add.at(depth, own[I <= J], 1.0)
+    depth += k * r + 4
+    for gid, D, B in lows:
+        WU, aWU = _hp_matmul(B.T, U64), _hp_matmul(np.abs(B).T, aU)
+        WV, aWV = (WU, aWU) if same else (_hp_matmul(B.T, V64), _hp_matmul(np.abs(B).T, aV))
+        q[gid] = np.sum(_ld(D)[:, None] * WU * WV) if WIDE else _hp_dot(np.repeat(D, r), (WU * WV).ravel())
+        mag[gid] = np.sum(np.abs(_ld(D))[:, None] * aWU * aWV)
+        depth[gid] = k * n * len(D) * r + r + 4
+    return dict(q=q, mag=mag, depth=depth)
+
+
+def fg_hp(C, As, bs, R, lam, lam_ub, sigma) -> dict:
+    """f! of src/coreop.jl:6-31 above FP64 from the matrices' own entries: v = 𝒜(RRᵀ) − b per constraint, obj = ⟨C, RRᵀ⟩,
+    ỹ = min(λ_ub, λ − σv), ℒ = obj + Σ(ỹ² − λ²)/(2σ) — with T[i] = Σ|a_jk|⟨|R_j|,|R_k|⟩ + |bᵢ| (a low-rank matrix:
+    Σ_c|d_c|·‖|b_c|ᵀ|R|‖² + |bᵢ|; index m the cost matrix) and the bounds of a correct FP64 evaluation in any summation order:
+      bound_v[i] = (r + Lᵢ + 4)·u·T[i]            (A_pair_hp's depth; n·s·r + r + 4 for a low-rank matrix)
+      bound_L    = (m + 6)·u·(|obj| + Σ(ỹ² + λ²)/(2σ)) + bound_v[m] + Σ|ỹᵢ|·bound_v[i] + σ/2·Σ bound_v[i]²
+    (ℒ depends on vᵢ through ỹᵢ²/(2σ), whose derivative is −ỹᵢ wherever the cap is not active and 0 where it is)."""
+    m = len(As)
+    a = A_pair_hp(C, As, R, R)
+    bl = _ld(bs)
+    v = a["q"].copy()
+    v[:m] -= bl
+    T = a["mag"].copy()
+    T[:m] += np.abs(bl)
+    bound_v = a["depth"] * LD(U53) * T
+    lam_, ub, sg = _ld(lam), _ld(lam_ub), LD(sigma)
+    yt = np.minimum(ub, lam_ - sg * v[:m])
+    obj = v[m]
+    L = obj + np.sum(yt * yt - lam_ * lam_) / (2 * sg)
+    Lmag = abs(obj) + np.sum(yt * yt + lam_ * lam_) / (2 * sg)
+    bound_L = (m + 6) * LD(U53) * Lmag + bound_v[m] + np.sum(np.abs(yt) * bound_v[:m]) + sg / 2 * np.sum(bound_v[:m] ** 2)
+    return dict(v=v, obj=obj, yt=yt, L=L, T=T, depth=a["depth"], bound_v=bound_v, bound_L=bound_L)
+
+
+def ytilde_from(pv_raw, lam, lam_ub, sigma) -> dict:
+    """ỹ = min(λ_ub, λ − σv) above FP64 from a given double v (the device's own primal_vio_raw), the bound 3u·(|λ| + σ|v|) of
+    its FP64 evaluation (one product, one difference, and a fused or unfused form of the two), and near = the entries whose
+    capping decision is within that bound of a tie without being one (either branch is then a correct answer)."""
+    m = len(lam)
+    lam_, ub, v, sg = _ld(lam), _ld(lam_ub), _ld(pv_raw)[:m], LD(sigma)
+    t = lam_ - sg * v
+    bound = 3 * LD(U53) * (np.abs(lam_) + sg * np.abs(v))
+    with np.errstate(invalid="ignore"):
+        near = np.asarray((np.abs(t - ub) <= bound) & (t != ub))        # (t = ub exactly: both branches give ub)
+    return dict(yt=np.minimum(ub, t), free=t, ub=ub, bound=bound, near=near, capped=np.asarray(t > ub))
+
+
+def device_pattern(C, As) -> dict:
+    """The pattern S is kept on (src/preprocess.jl:24-169), rebuilt here from the matrices' own entries: the union of the sparse
+    matrices' upper-triangular entries in CSC order (V_TRIU_S_NZVAL), the union of all their entries in CSC order (V_S_NZVAL),
+    each full entry's position (min, max) in the upper one, and per aggregated entry its position and owner."""
+    n = C.shape[0]
+    (I, J, W, own), lows = split_matrices(C, As)
+    up = I <= J
+    keyT = np.unique(J[up] * n + I[up])
+    keyF = np.unique(J * n + I)
+    fr, fc = keyF % n, keyF // n
+    mapped = np.searchsorted(keyT, np.maximum(fr, fc) * n + np.minimum(fr, fc))
+    assert keyF.size == 0 or np.array_equal(keyT[mapped], np.maximum(fr, fc) * n + np.minimum(fr, fc)), "an entry without its mirror"
+    pos = np.searchsorted(keyT, J[up] * n + I[up])
+    return dict(n=n, nnzT=int(keyT.size), nnzS=int(keyF.size), t_row=keyT % n, t_col=keyT // n, f_row=fr, f_col=fc,
+                mapped=mapped, pos=pos, own=own[up], val=W[up], lows=lows)
+
+
+def S_and_G_hp(C, As, y, R, pattern=None, with_G=True) -> dict:
+    """From a given double y (the device's own; y[m] the cost matrix's coefficient) above FP64: the entries of S = Σ y_k·A_k on
+    the device's pattern (upper and full; the low-rank terms are not part of it), G = 2·(S + Σ y_k·B_kD_kB_kᵀ)·R, and the scales
+      S_mag[e] = Σ_k |y_k||a_k,e|,  G_mag = 2·(|S|_termwise·|R|)   (a low-rank term as |y_k|·|B||D|(|B|ᵀ|R|))
+    with the bounds of a correct FP64 evaluation in any summation order:
+      bound_S[e] = (c_e + 2)·u·S_mag[e]     c_e the stored entries (of all matrices, duplicates counted) that fall on e
+      bound_G[j] = (d_j + c_max + s_tot + 4)·u·G_mag[j]   d_j the length of row j of S (n where a low-rank term is present: its
+                   projection Bᵀ R sums n products), s_tot the low-rank columns."""
+    p = pattern or device_pattern(C, As)
+    n = p["n"]
+    R64 = np.asarray(R, dtype=np.float64)
+    r = R64.shape[1]
+    y64 = np.asarray(y, dtype=np.float64)
+    u = LD(U53)
+    St = _hp_segsum(p["val"], _ld(y64[p["own"]]), p["pos"], p["nnzT"])
+    Sm = _hp_segsum(np.abs(p["val"]), np.abs(_ld(y64[p["own"]])), p["pos"], p["nnzT"])
+    ce = np.bincount(p["pos"], minlength=p["nnzT"]).astype(np.float64)
+    out = dict(pattern=p, triu=St, triu_mag=Sm, c=ce, bound_triu=(ce + 2) * u * Sm,
+               full=St[p["mapped"]], full_mag=Sm[p["mapped"]], bound_full=((ce + 2) * u * Sm)[p["mapped"]])
+    if not with_G:
+        return out
+    ty = LD if WIDE else np.float64
+    G, Gm = np.zeros((n, r), dtype=ty), np.zeros((n, r), dtype=ty)
+    if p["nnzS"]:
+        # column j of the full pattern: G_j += S_e·R_row (𝒜t!(y, x, aux, var), src/coreop.jl:260-279); the entries are sorted by
+        # column, so every row of G is one contiguous segment (no running sum across rows of very different size)
+        starts = np.flatnonzero(np.diff(np.concatenate([[-1], p["f_col"]])))
+        cols = p["f_col"][starts]
+        if WIDE:
+            G[cols] = np.add.reduceat(out["full"][:, None] * _ld(R64)[p["f_row"]], starts, axis=0)
+            Gm[cols] = np.add.reduceat(out["full_mag"][:, None] * np.abs(_ld(R64))[p["f_row"]], starts, axis=0)
+        else:
+            S64 = sp.csc_matrix((np.asarray(out["full"], dtype=np.float64), (p["f_col"], p["f_row"])), shape=(n, n)).toarray()
+            Sm64 = sp.csc_matrix((np.asarray(out["full_mag"], dtype=np.float64), (p["f_col"], p["f_row"])), shape=(n, n)).toarray()
+            G, Gm = _hp_matmul(S64, R64), _hp_matmul(Sm64, np.abs(R64))
+    s_tot = 0
+    for gid, D, B in p["lows"]:
+        s_tot += len(D)
+        W, Wm = _hp_matmul(B.T, R64), _hp_matmul(np.abs(B).T, np.abs(R64))
+        for c in range(len(D)):        # (one outer product per column, in the wide type)
+            G = G + (ty(y64[gid]) * ty(D[c]) * B[:, c].astype(ty))[:, None] * W[c][None, :].astype(ty)
+            Gm = Gm + (abs(ty(y64[gid]) * ty(D[c])) * np.abs(B[:, c]).astype(ty))[:, None] * Wm[c][None, :].astype(ty)
+    d = np.full(n, float(n)) if p["lows"] else np.bincount(p["f_col"], minlength=n).astype(np.float64)
+    cmax = float(ce.max()) if ce.size else 0.0
+    out.update(G=2 * G, G_mag=2 * Gm, d=d, bound_G=((d + cmax + s_tot + 4) * u)[:, None] * (2 * Gm))
+    return out
+
+
+def worst_ratio(got, want, bound) -> float:
+    """max |got − want|/bound over EVERY element; an element whose bound is 0 must be exact (else inf)."""
+    err = np.abs(_ld(got) - np.asarray(want, dtype=LD))
+    bound = np.asarray(bound, dtype=LD)
+    if err.size == 0:
+        return 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.where(err == 0, 0.0, np.inf))
+    ratio = np.where(np.isnan(ratio), np.inf, ratio)
+    return float(np.max(ratio))

@@ -362,8 +362,8 @@ def test_alpha_and_L_through_one_iteration(hip_abi, monkeypatch, family, route):
     r, h = (8 if family == "maxcut300" else 3), 4
     rng = np.random.Generator(np.random.PCG64(61))
     lam = [0.1 * rng.standard_normal(d.m) for d in datas]
-    # the state before the step, from twin handles on the plain route (fg! is the same state on every route: pinned elsewhere
-    # to 1e-11; here only R, λ and what f! left are read, and G of the very handle that steps — below)
+    # the state before the step, from twin handles on the plain route (fg! is the same state on every route: pinned above FP64
+    # in tests/test_gpu_fg_operators.py; here only R, λ and what f! left are read, and G of the very handle that steps — below)
     _set_route(monkeypatch, route)
     S = [make_solver(hip_abi, d, r, seed=11, h=h)[0] for d in datas]
     norms = [(d.normC(), float(np.linalg.norm(d.b))) for d in datas]
