@@ -50,6 +50,10 @@ def main():
     ap.add_argument("--batch", default=None, help="manifest written by scripts/gen_batch_test.py")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--passes", type=int, default=2, help="passes over the batch; the last one is `wall_s`")
+    ap.add_argument("--rounding", choices=("none", "host", "device"), default="none",
+                    help="the reference runner's rounding callback after every solve (exps/test.jl:132; MaxCut and "
+                         "MinimumBisection): on the device — lockstep: one sdplr_hip_batch_round for the whole batch — or with "
+                         "the rounding.py callbacks on the downloaded factor; adds `callback_res` to the result")
     args = ap.parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # launcher: before this process touches torch or the HIP library (see bench.py)
@@ -60,7 +64,7 @@ def main():
             port = so.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus)]
-        cmd += ["--passes", str(args.passes)]
+        cmd += ["--passes", str(args.passes), "--rounding", args.rounding]
         if args.batch:
             cmd += ["--batch", args.batch]
         sys.exit(subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))))
@@ -102,23 +106,31 @@ def main():
     # Two passes over the batch: the first one also fills the library's pools (streams, pinned blocks, device blocks of the
     # sizes this batch uses — a lockstep batch has all its handles alive at once), the second one is the steady state of a
     # process that solves batch after batch.  Both walls are reported.
+    kind = {"MaxCut": "maxcut", "MinimumBisection": "bisection"}.get(e0["problem"])
+    if args.rounding != "none" and kind is None:
+        sys.exit(f"run_batch.py: --rounding needs a MaxCut or MinimumBisection batch, not {e0['problem']}")
     walls = []
     for _ in range(max(1, args.passes)):
+        # (a fresh generator per instance and pass, seeded as the solve: every pass rounds with the same draws)
+        rnd = None if args.rounding == "none" else [
+            (kind, g, np.random.Generator(np.random.PCG64(e0["seed"] + k))) if k in mine else None for k, g in enumerate(graphs)]
         if dist is not None:
             dist.barrier()
         t0 = time.perf_counter()
         local = batch.solve_local(datas, rank, world, e0["rank"], concurrency=conc, lockstep=lockstep,
-                                  ptol=e0["ptol"], objtol=e0["objtol"], seed=e0["seed"], prior_trace_bound=tb)
+                                  ptol=e0["ptol"], objtol=e0["objtol"], seed=e0["seed"], prior_trace_bound=tb,
+                                  **({} if rnd is None else dict(rounding=rnd, rounding_on=args.rounding)))
         res = batch.gather(local, len(graphs), dist, device)
         walls.append(time.perf_counter() - t0)
     dt = walls[-1]
     if rank == 0:
+        extra = {} if args.rounding == "none" else {"rounding": args.rounding, "callback_res": [float(x) for x in res[:, 5]]}
         print(json.dumps({"instances": len(graphs), "n_gpus": world, "wall_s": dt, "first_pass_wall_s": walls[0],
                           "problem_build_s": build_s,
                           "mode": "lockstep" if lockstep else "threads", "in_flight_per_gpu": conc, "instances_per_s": len(graphs) / dt,
                           "objectives": [round(x, 4) for x in res[:, 1]],
                           "dual_bounds": [round(x, 4) for x in res[:, 2]],
-                          "iterations": [int(x) for x in res[:, 3]]}))
+                          "iterations": [int(x) for x in res[:, 3]], **extra}))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

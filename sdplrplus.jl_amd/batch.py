@@ -25,30 +25,53 @@ def assign(n_instances: int, world: int) -> List[List[int]]:
 
 
 def solve_local(instances: Sequence, rank: int, world: int, r: int, *, abi=None, concurrency: int = 8,
-                make_data: Optional[Callable] = None, lockstep: bool = False, **kwargs) -> np.ndarray:
+                make_data: Optional[Callable] = None, lockstep: bool = False, rounding: Optional[Sequence] = None,
+                rounding_on: str = "device", **kwargs) -> np.ndarray:
     """Solve this rank's share.  `instances[k]` is an SDPData, or anything `make_data` turns into one.
     ``lockstep``: side by side through ``solve_lockstep`` (one launch per step for all of them) instead of as
-    ``concurrency`` independent driver threads.  Returns an array [n_local, N_FIELDS]."""
+    ``concurrency`` independent driver threads.  Returns an array [n_local, N_FIELDS].
+    ``rounding``: per instance ``("maxcut" | "bisection", A, rng)`` — the reference runner's callback after every solve
+    (exps/test.jl:132); its value is a further column (N_FIELDS + 1).  ``rounding_on``: "device" (lockstep: one
+    ``batch_round`` for the whole share; threads: the ``*_rounding_device`` callback on each live handle) or "host" (the
+    ``rounding.py`` callbacks on the downloaded factor)."""
+    from . import rounding as _rounding
     mine = assign(len(instances), world)[rank]
+    nf = N_FIELDS + (rounding is not None)
+    host_fn = {"maxcut": _rounding.maxcut_rounding, "bisection": _rounding.minimumbisection_rounding}
+    dev_fn = {"maxcut": _rounding.maxcut_rounding_device, "bisection": _rounding.minimumbisection_rounding_device}
+    if rounding is not None and rounding_on not in ("device", "host"):
+        raise ValueError('rounding_on must be "device" or "host"')
     if lockstep and mine:
         datas = [make_data(instances[k]) if make_data is not None else instances[k] for k in mine]
         # (set-up threads: 64 config-5 instances take 78 / 24 / 15 / 14 / 20 ms on 1 / 4 / 8 / 12 / 16 threads —
         # scripts/probes/setup_scaling.py: beyond ≈ 8 the HIP runtime's own locks and the GIL take the gain back)
-        res = solve_lockstep(datas, r, abi=abi, setup_workers=min(concurrency, 8), printlevel=0, **kwargs)
+        on_device = rounding is not None and rounding_on == "device"
+        res = solve_lockstep(datas, r, abi=abi, setup_workers=min(concurrency, 8), printlevel=0,
+                             rounding=[rounding[k] for k in mine] if on_device else None, **kwargs)
         for x in res:
             if isinstance(x, Exception):
                 raise x
-        return np.asarray([[float(k), x["obj"], x["max_dual_value"], float(x["iter"]), x["totaltime"]]
-                           for k, x in zip(mine, res)], dtype=np.float64)
+        rows = [[float(k), x["obj"], x["max_dual_value"], float(x["iter"]), x["totaltime"]] for k, x in zip(mine, res)]
+        if rounding is not None:
+            for row, k, x in zip(rows, mine, res):
+                kind, A, rng = rounding[k]
+                row.append(x["callback_res"] if on_device else host_fn[kind](A, x["Rt"], rng))
+        return np.asarray(rows, dtype=np.float64)
 
     def one(k):
         data = make_data(instances[k]) if make_data is not None else instances[k]
         t0 = time.perf_counter()
-        res = sdplr(data=data, r=r, abi=abi, printlevel=0, **kwargs)
-        return [float(k), res["obj"], res["max_dual_value"], float(res["iter"]), time.perf_counter() - t0]
+        cb = None
+        if rounding is not None:
+            kind, A, rng = rounding[k]
+            cb = (lambda var, d: dev_fn[kind](var, A, rng)) if rounding_on == "device" else \
+                (lambda var, d: host_fn[kind](A, var.Rt, rng))
+        res = sdplr(data=data, r=r, abi=abi, printlevel=0, callback=cb, **kwargs)
+        row = [float(k), res["obj"], res["max_dual_value"], float(res["iter"]), time.perf_counter() - t0]
+        return row + ([res["callback_res"]] if rounding is not None else [])
 
     if not mine:
-        return np.zeros((0, N_FIELDS))
+        return np.zeros((0, nf))
     if concurrency <= 1 or len(mine) == 1:
         rows = [one(k) for k in mine]
     else:  # ctypes releases the GIL inside the library, so the handles' streams really overlap
@@ -165,7 +188,8 @@ def serve_batch(abi, solvers, reqs) -> list:
 
 
 def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8, iteration_cap: Optional[int] = None,
-                   overlap_setup: Optional[bool] = None, **kwargs) -> list:
+                   overlap_setup: Optional[bool] = None, rounding: Optional[Sequence] = None, rounding_trials: int = 100,
+                   **kwargs) -> list:
     """``sdplr`` on every SDPData of ``datas`` side by side on ONE device: the solves advance in lockstep — each round
     serves the pending device step of all live instances as one call (``serve_batch``) — instead of as independent
     threads whose launches share the GPU only as far as its hardware queues allow.  Same control flow (``sdplr_steps``),
@@ -175,7 +199,15 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
     ``maxtime`` budget it is tested against) starts at its first step and keeps running while the other instances of the
     round are served, so every instance reports roughly the whole batch's wall (plus the mean set-up time).  Iterations,
     objective, dual bound, R and λ are those of the one-by-one solve, bit for bit.  All handles live on the calling thread's
-    device (``abi.set_device`` is sticky: the set-up threads and the library's own workers bind to it)."""
+    device (``abi.set_device`` is sticky: the set-up threads and the library's own workers bind to it).
+
+    ``rounding``: None (the default: handles close as their solves end, no further keys), or per instance
+    ``("maxcut" | "bisection", A, rng)`` — the reference runner's rounding callback (exps/test.jl:132).  Every handle then
+    stays open until the last solve has ended, all solutions are rounded on the device in ONE ``batch_round``
+    (``rounding.batch_rounding_device``: ``rounding_trials`` draws from each instance's ``rng``), and each result gets
+    ``callback_res`` — what ``sdplr(..., callback=)`` with the ``*_rounding_device`` callback returns, bit for bit — and
+    ``callback_time`` (the wall of the batch's one call).  An instance whose solve failed keeps its exception and is left
+    out.  Iterations, objective, R and λ do not depend on it."""
     abi = abi if abi is not None else cabi.load_hip()
 
     def config_of():
@@ -191,6 +223,8 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
     from concurrent.futures import FIRST_COMPLETED, wait
     configs = [config_of() for _ in datas]
     n_inst = len(datas)
+    if rounding is not None and len(rounding) != n_inst:
+        raise ValueError("rounding must name one (kind, A, rng) per instance")
     results: list = [None] * n_inst
     solvers: list = [None] * n_inst
     steppers: list = [None] * n_inst
@@ -229,7 +263,8 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
             ans["preprocess_time"] = setup_s[k]
             ans["totaltime"] += setup_s[k]
             results[k] = ans
-            solvers[k].close()
+            if rounding is None:
+                solvers[k].close()
         except Exception as e:
             pending.pop(k, None)
             results[k] = e
@@ -273,6 +308,19 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
                 response = cap.incoming(k, response)
                 if response is not None:
                     advance(k, response)
+        if rounding is not None:
+            from . import rounding as _rounding
+            ks = [k for k in range(n_inst) if isinstance(results[k], dict)]
+            tc = time.time()
+            cuts = _rounding.batch_rounding_device([solvers[k] for k in ks], [rounding[k][1] for k in ks],
+                                                   [rounding[k][2] for k in ks], [rounding[k][0] for k in ks],
+                                                   trials=rounding_trials, abi=abi)
+            tc = time.time() - tc
+            for k, c in zip(ks, cuts):
+                if isinstance(c, Exception):
+                    results[k] = c
+                else:
+                    results[k]["callback_res"], results[k]["callback_time"] = c, tc
     finally:
         if ex is not None:
             for f in list(waiting):
@@ -288,14 +336,15 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
 
 
 def gather(local: np.ndarray, n_instances: int, dist=None, device=None) -> np.ndarray:
-    """All ranks' result rows, ordered by instance index ([n_instances, N_FIELDS]) — one all_gather."""
+    """All ranks' result rows, ordered by instance index ([n_instances, N_FIELDS], or as many columns as ``local`` has)
+    — one all_gather."""
     if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
         out = local
     else:
         import torch
         world = dist.get_world_size()
         cap = (n_instances + world - 1) // world
-        buf = torch.full((cap, N_FIELDS), float("nan"), dtype=torch.float64, device=device)
+        buf = torch.full((cap, local.shape[1]), float("nan"), dtype=torch.float64, device=device)
         if local.shape[0]:
             buf[: local.shape[0]] = torch.as_tensor(local, dtype=torch.float64, device=device)
         parts = [torch.empty_like(buf) for _ in range(world)]

@@ -131,6 +131,19 @@ ROUND_HYPERPLANE, ROUND_BISECTION = 0, 1
 ROUND_MAX_TRIALS = 4096
 
 
+class RoundItem(C.Structure):         # sdplr_hip_round_item
+    _fields_ = [("s", _vp), ("mode", _i32), ("slot", _i32), ("trials", _i64), ("gauss", _pf64), ("cuts", _pf64),
+                ("best", _i64), ("x_best", _pi8), ("labels", _pi8), ("route", _i32), ("status", _i32)]
+
+
+# include/sdplr_hip_round_batch.h (the rounding of a whole batch in one call), checked against that header by
+# tests/test_round_batch_cabi.py.  A further extension, bound only when the library exports it.
+ROUND_BATCH_SIGNATURES = {
+    "batch_round": [_i32, C.POINTER(RoundItem)],
+}
+ROUND_ROUTE_SINGLE, ROUND_ROUTE_SHARED = 0, 1
+
+
 class SdplrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[{code}] {msg}")
@@ -156,6 +169,13 @@ class CABI:
         self.has_round = all(hasattr(self.lib, prefix + name) for name in ROUND_SIGNATURES)
         if self.has_round:
             for name, argtypes in ROUND_SIGNATURES.items():
+                fn = getattr(self.lib, prefix + name)
+                fn.argtypes = argtypes
+                fn.restype = _i32
+                setattr(self, name, fn)
+        self.has_round_batch = self.has_round and all(hasattr(self.lib, prefix + name) for name in ROUND_BATCH_SIGNATURES)
+        if self.has_round_batch:
+            for name, argtypes in ROUND_BATCH_SIGNATURES.items():
                 fn = getattr(self.lib, prefix + name)
                 fn.argtypes = argtypes
                 fn.restype = _i32
@@ -650,3 +670,39 @@ def batch_dual_obj(abi: CABI, solvers, args):
     rc = abi.batch_dual_obj(len(solvers), arr)
     out = _batch_results(abi, arr, solvers, lambda q: (q.dual_value, q.mineig), rc)
     return [o if isinstance(o, Exception) else o + (ys[k],) for k, o in enumerate(out)]
+
+
+def batch_round(abi: CABI, solvers, requests):
+    """``round`` of every solver in one call (include/sdplr_hip_round_batch.h); requests[k] =
+    (mode, trials, gauss[, slot[, want_best[, want_labels]]]) with the meanings of ``Solver.round``.
+    → per solver (cuts[trials], best index, x_best or None, labels or None, route) — route 1: served by the shared launch,
+    0: by the single-instance call — or the SdplrError its own call would have raised."""
+    if not getattr(abi, "has_round_batch", False):
+        raise NotImplementedError(f"{abi.path} does not export the batch rounding entry point")
+    arr = (RoundItem * len(solvers))()
+    keep = []
+    for k, (sv, q) in enumerate(zip(solvers, requests)):
+        mode, trials, gauss, slot, want_best, want_labels = tuple(q) + (F_RT, False, False)[len(q) - 3:]
+        trials = int(trials)
+        g = _f64c(gauss)
+        if g.shape != (trials, sv.r):
+            raise ValueError(f"gauss of item {k} must have shape (trials, r) = ({trials}, {sv.r}), got {g.shape}")
+        cuts = np.zeros(max(trials, 1))
+        xb = np.zeros(sv.n, dtype=np.int8) if want_best else None
+        lab = np.zeros((max(trials, 1), sv.n), dtype=np.int8) if want_labels else None
+        keep.append((g, cuts, xb, lab, trials))
+        it = arr[k]
+        it.s = sv._h.value
+        it.mode, it.slot, it.trials, it.gauss, it.cuts, it.best = int(mode), int(slot), trials, _pd(g), _pd(cuts), -1
+        it.x_best = xb.ctypes.data_as(_pi8) if want_best else None
+        it.labels = lab.ctypes.data_as(_pi8) if want_labels else None
+    rc = abi.batch_round(len(solvers), arr)
+    out = _batch_results(abi, arr, solvers, lambda q: q, rc)
+    res = []
+    for k, o in enumerate(out):
+        if isinstance(o, Exception):
+            res.append(o)
+            continue
+        _, cuts, xb, lab, trials = keep[k]
+        res.append((cuts[:trials], int(arr[k].best), xb, (lab[:trials] if lab is not None else None), int(arr[k].route)))
+    return res

@@ -3,6 +3,7 @@
 // HBM + one HIP stream.  There is no CPU fallback: without a device every entry point fails.
 #include "../../include/sdplr_hip.h"
 #include "../../include/sdplr_hip_round.h"
+#include "../../include/sdplr_hip_round_batch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -33,6 +34,7 @@
 #include "k_resident.h"
 #include "k_group.h"
 #include "k_round.h"
+#include "k_round_batch.h"
 
 namespace {
 
@@ -238,7 +240,9 @@ struct sdplr_hip_solver {
     long long E = 0;
     int *ei = nullptr, *ej = nullptr;
     double* ew = nullptr;
-    enum { LAB, KEYS, GT, PART, CUTS, SELK, SELCUT, OUT8, NBUF };
+    enum { LAB, KEYS, GT, PART, CUTS, SELK, SELCUT, OUT8,
+           B_TAB, B_LAB, B_CUTS, B_LTAB, B_OUT8,   // sdplr_hip_batch_round: the first handle of a call holds the batch's work arrays
+           NBUF };
     void* buf[NBUF] = {};
     size_t cap[NBUF] = {};
   } rd;
@@ -5263,6 +5267,166 @@ int32_t sdplr_hip_batch_dual_obj(int32_t count, sdplr_hip_dual_item* it) {
     if (!q.s) { q.status = SDPLR_ERR_INVALID_ARG; return; }
     q.status = sdplr_hip_dual_obj(q.s, q.trace_bound, q.iter, q.v0, &q.dual_value, &q.mineig);
     if (!q.status && q.y_out) q.status = sdplr_hip_get_vec(q.s, SDPLR_V_Y, q.y_out, q.s->m + 1);
+  });
+  for (int i = 0; i < count; i++) if (it[i].status) return it[i].status;
+  return SDPLR_OK;
+}
+
+}  // extern "C"
+
+// ---- rounding a whole batch (include/sdplr_hip_round_batch.h, k_round_batch.h) ------------------------------------------
+// Like sdplr_hip_round, the call leaves every solver's state alone.  The shared grid runs on the first taken handle's
+// stream and reads the other handles' R with no event dependency: batch_round_trip's invariant (every entry point drains
+// its handle's stream before it returns) covers it, and a slot that ensure_dirt had to refresh is waited for below.
+namespace {
+struct RoundBatchRow {   // an item the shared launch takes
+  int item;
+  const double* R;
+  int n, r, T, W, Tpad;
+  size_t g_off, lab_off, cuts_off;   // into the Γ part of the table (doubles), the label words (words), the cuts (doubles)
+};
+// the R of sdplr_hip_round's `slot`, current in HBM; nullptr when that call would fail (it then reports the item's status)
+const double* round_batch_factor(S* s, int32_t slot) {
+  if (slot == SDPLR_F_RT) return aslot(s->arena, AS_R);
+  const bool scratch = slot == SDPLR_F_SCRATCH || slot == SDPLR_F_SCRATCH + 1;
+  if (!scratch && factor_ptr(s, slot) != nullptr && ensure_dirt(s)) return nullptr;
+  const double* R = factor_ptr(s, slot);
+  // (ensure_dirt, or the zero fill of a fresh scratch slot, may be in flight on this handle's stream: the grid runs on another)
+  if (R && hipStreamSynchronize(s->stream) != hipSuccess) return nullptr;
+  return R;
+}
+int round_batch_shared(sdplr_hip_round_item* it, std::vector<RoundBatchRow>& rows) {
+  using Rd = S::Round;
+  S* s = it[rows[0].item].s;   // the leader: its stream carries the launches, its pool holds the work arrays
+  const size_t B = rows.size();
+  size_t nblk = 0, g_doubles = 0, lab_words = 0, cut_doubles = 0, lds = 0;
+  for (RoundBatchRow& q : rows) {
+    q.g_off = g_doubles; q.lab_off = lab_words; q.cuts_off = cut_doubles;
+    nblk += q.W; g_doubles += (size_t)q.r * q.Tpad; lab_words += (size_t)q.n * q.W; cut_doubles += q.Tpad;
+    lds = std::max(lds, round_batch_lds(q.n, q.r, it[q.item].mode));
+  }
+  const size_t o_blk = batch_up(B * sizeof(RoundBatchArgs)), o_g = o_blk + batch_up(nblk * sizeof(RoundBatchBlock)),
+               tab_bytes = o_g + g_doubles * sizeof(double);
+  int rc;
+  if ((rc = round_reserve(s, Rd::B_TAB, tab_bytes)) || (rc = round_reserve(s, Rd::B_LAB, lab_words * sizeof(round_u64))) ||
+      (rc = round_reserve(s, Rd::B_CUTS, cut_doubles * sizeof(double)))) return rc;
+  char* dtab = (char*)s->rd.buf[Rd::B_TAB];
+  round_u64* dlab = (round_u64*)s->rd.buf[Rd::B_LAB];
+  double* dcuts = (double*)s->rd.buf[Rd::B_CUTS];
+  std::vector<char> tab(tab_bytes, 0);   // arguments, block map and Γ of the whole batch: one copy up
+  {
+    RoundBatchArgs* args = reinterpret_cast<RoundBatchArgs*>(tab.data());
+    RoundBatchBlock* blk = reinterpret_cast<RoundBatchBlock*>(tab.data() + o_blk);
+    double* g = reinterpret_cast<double*>(tab.data() + o_g);
+    size_t b = 0;
+    for (size_t k = 0; k < B; k++) {
+      const RoundBatchRow& q = rows[k];
+      const sdplr_hip_round_item& x = it[q.item];
+      const S* sk = x.s;
+      RoundBatchArgs a{};
+      a.R = q.R; a.gT = reinterpret_cast<const double*>(dtab + o_g) + q.g_off;
+      a.ei = sk->rd.ei; a.ej = sk->rd.ej; a.ew = sk->rd.ew; a.E = sk->rd.E;
+      a.lab = dlab + q.lab_off; a.cuts = dcuts + q.cuts_off;
+      a.n = q.n; a.r = q.r; a.T = q.T; a.Tpad = q.Tpad; a.W = q.W; a.mode = x.mode;
+      a.nb_score = blocks_for(sk->rd.E, 64 * (SDPLR_NT / 64) * 4, SDPLR_ROUND_SCORE_NB);   // sdplr_hip_round's scoring grid: the summation order
+      args[k] = a;
+      for (int w = 0; w < q.W; w++) blk[b++] = RoundBatchBlock{(int)k, w};
+      double* h = g + q.g_off;   // Γ transposed, zeros beyond T
+      for (int t = 0; t < q.T; t++)
+        for (int j = 0; j < q.r; j++) h[(size_t)j * q.Tpad + t] = x.gauss[(size_t)t * q.r + j];
+    }
+  }
+  if ((rc = h2d_copy(s, dtab, tab.data(), tab_bytes))) return rc;
+  RS_SET_ATTR(k_round_batch);
+  k_round_batch<<<(unsigned int)nblk, SDPLR_ROUND_BATCH_NT, lds, s->stream>>>(reinterpret_cast<const RoundBatchArgs*>(dtab),
+                                                                            reinterpret_cast<const RoundBatchBlock*>(dtab + o_blk));
+  HIPCK(s, hipGetLastError());
+  std::vector<double> hcuts(cut_doubles);
+  HIPCK(s, hipMemcpyAsync(hcuts.data(), dcuts, cut_doubles * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIPCK(s, hipStreamSynchronize(s->stream));
+  std::vector<RoundBatchLabelArgs> lt;
+  std::vector<std::pair<int8_t*, size_t>> dst;   // where each request's bytes go
+  size_t out_bytes = 0;
+  for (const RoundBatchRow& q : rows) {
+    sdplr_hip_round_item& x = it[q.item];
+    memcpy(x.cuts, hcuts.data() + q.cuts_off, (size_t)q.T * sizeof(double));
+    int64_t b = 0;
+    for (int t = 1; t < q.T; t++)
+      if (x.mode == 0 ? x.cuts[t] > x.cuts[b] : x.cuts[t] < x.cuts[b]) b = t;
+    x.best = b;
+    for (int pass = 0; pass < 2; pass++) {
+      int8_t* d = pass == 0 ? x.x_best : x.labels;
+      if (!d) continue;
+      const int t0 = pass == 0 ? (int)b : 0, nt = pass == 0 ? 1 : q.T;
+      lt.push_back(RoundBatchLabelArgs{dlab + q.lab_off, reinterpret_cast<signed char*>(out_bytes), q.n, q.W, t0, nt});   // (out: an offset until the array is reserved)
+      dst.emplace_back(d, (size_t)q.n * nt);
+      out_bytes += (size_t)q.n * nt;
+    }
+  }
+  if (!lt.empty()) {   // x_best / labels of the whole batch: one more launch, one more copy
+    if ((rc = round_reserve(s, Rd::B_OUT8, out_bytes)) || (rc = round_reserve(s, Rd::B_LTAB, lt.size() * sizeof(RoundBatchLabelArgs)))) return rc;
+    signed char* out8 = (signed char*)s->rd.buf[Rd::B_OUT8];
+    for (RoundBatchLabelArgs& a : lt) a.out = out8 + reinterpret_cast<size_t>(a.out);
+    if ((rc = h2d_copy(s, s->rd.buf[Rd::B_LTAB], lt.data(), lt.size() * sizeof(RoundBatchLabelArgs)))) return rc;
+    k_round_batch_labels<<<dim3((unsigned int)lt.size(), SDPLR_ROUND_BATCH_LABEL_NY), SDPLR_NT, 0, s->stream>>>(
+        reinterpret_cast<const RoundBatchLabelArgs*>(s->rd.buf[Rd::B_LTAB]));
+    HIPCK(s, hipGetLastError());
+    std::vector<int8_t> h8(out_bytes);
+    HIPCK(s, hipMemcpyAsync(h8.data(), out8, out_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIPCK(s, hipStreamSynchronize(s->stream));
+    size_t o = 0;
+    for (auto& d : dst) { memcpy(d.first, h8.data() + o, d.second); o += d.second; }
+  }
+  return SDPLR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t sdplr_hip_batch_round(int32_t count, sdplr_hip_round_item* it) {
+  if (count < 0 || (count > 0 && !it)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_round: bad args");
+  if (have_device() <= 0) return fail(nullptr, SDPLR_ERR_NO_DEVICE, "no usable HIP device (libsdplr_hip has no CPU fallback)");
+  std::vector<int> single;
+  {
+    std::vector<const S*> hs;
+    for (int i = 0; i < count; i++) hs.push_back(it[i].s);
+    if (!batch_handles_distinct(hs)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_round: a handle appears twice");   // (before any handle is dereferenced or any item written)
+    int dev = -1;
+    if (!batch_one_device(hs, &dev)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_round: the handles live on different devices");
+    // an item keeps SDPLR_ERR_UNSERVED until it has actually been served
+    for (int i = 0; i < count; i++) { it[i].status = SDPLR_ERR_UNSERVED; it[i].route = 0; }
+    ApiShared api_guard(dev);
+    long long nmax = SDPLR_ROUND_BATCH_NMAX;
+    if (const char* e = getenv("SDPLR_HIP_BATCH_ROUND_NMAX")) nmax = std::max(0LL, std::min(nmax, atoll(e)));
+    const char* off_env = getenv("SDPLR_HIP_NO_BATCH_ROUND");
+    const bool off = off_env != nullptr && atoi(off_env) != 0;
+    std::vector<RoundBatchRow> rows;
+    for (int i = 0; i < count; i++) {
+      const sdplr_hip_round_item& q = it[i];
+      S* s = q.s;
+      // whatever sdplr_hip_round would refuse goes to that call, which reports the item's status
+      const bool ok = !off && s && s->finalized && s->rd.have_graph && !s->prof_on && (q.mode == 0 || q.mode == 1) && q.trials >= 1 &&
+                      q.trials <= 4096 && q.gauss && q.cuts && s->n <= nmax && round_batch_lds(s->n, s->r, q.mode) <= RS_LDS_MAX;
+      const double* R = ok ? round_batch_factor(s, q.slot) : nullptr;
+      if (!R) { single.push_back(i); continue; }
+      const int T = (int)q.trials, W = (T + 63) / 64;
+      rows.push_back(RoundBatchRow{i, R, (int)s->n, (int)s->r, T, W, 64 * W, 0, 0, 0});
+    }
+    if (!rows.empty()) {
+      const int rc = round_batch_shared(it, rows);
+      S* lead = it[rows[0].item].s;
+      for (const RoundBatchRow& q : rows) {
+        sdplr_hip_round_item& x = it[q.item];
+        x.status = rc;
+        x.route = 1;
+        if (rc && x.s != lead) x.s->err = lead->err;
+      }
+    }
+  }
+  run_singles(single, [&](int i) {
+    sdplr_hip_round_item& q = it[i];
+    if (!q.s) { q.status = SDPLR_ERR_INVALID_ARG; return; }
+    q.status = sdplr_hip_round(q.s, q.mode, q.slot, q.trials, q.gauss, q.cuts, &q.best, q.x_best, q.labels);
   });
   for (int i = 0; i < count; i++) if (it[i].status) return it[i].status;
   return SDPLR_OK;

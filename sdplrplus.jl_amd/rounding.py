@@ -38,15 +38,19 @@ def minimumbisection_rounding(A, R: np.ndarray, rng: np.random.Generator, trials
     return best
 
 
+def _gauss(rng: np.random.Generator, trials: int, r: int) -> np.ndarray:
+    gauss = np.empty((trials, r))
+    for t in range(trials):                  # one draw per trial, as the host callbacks consume the generator
+        gauss[t] = rng.standard_normal(r)
+    return gauss
+
+
 def _round_device(var, A, rng: np.random.Generator, trials: int, mode: int) -> float:
     from . import cabi
     if trials > cabi.ROUND_MAX_TRIALS:
         raise ValueError(f"at most {cabi.ROUND_MAX_TRIALS} trials per call")
     var.round_set_graph(A)
-    gauss = np.empty((trials, var.r))
-    for t in range(trials):                  # one draw per trial, as the host callbacks consume the generator
-        gauss[t] = rng.standard_normal(var.r)
-    cuts, best, _, _ = var.round(mode, trials, gauss)
+    cuts, best, _, _ = var.round(mode, trials, _gauss(rng, trials, var.r))
     return float(cuts[best])
 
 
@@ -59,3 +63,41 @@ def maxcut_rounding_device(var, A, rng: np.random.Generator, trials: int = 100) 
 def minimumbisection_rounding_device(var, A, rng: np.random.Generator, trials: int = 100) -> float:
     """``minimumbisection_rounding`` on the device, on the factor R of the live handle ``var``."""
     return _round_device(var, A, rng, trials, 1)
+
+
+ROUNDING_MODES = {"maxcut": 0, "bisection": 1}
+
+
+def batch_rounding_device(vars, As, rngs, mode, trials: int = 100, abi=None, routes=None, loop: bool = False) -> list:
+    """The ``*_device`` callbacks for a whole batch of live handles in ONE library call (include/sdplr_hip_round_batch.h):
+    ``vars[k]`` is rounded on graph ``As[k]`` with the draws of ``rngs[k]``; ``mode`` is "maxcut" | "bisection" (or 0 | 1), one
+    for all or one per instance.  Each graph is uploaded once, each instance takes the draws its own callback would take.
+    → the best cut per instance, bit for bit what ``maxcut_rounding_device`` / ``minimumbisection_rounding_device`` return
+    (an instance whose item failed: its exception).  ``routes``: a list that receives what served each item (1: the shared
+    launch, 0: the single-instance call).  ``loop=True`` makes the calls one by one instead (A/B runs)."""
+    from . import cabi
+    vars = list(vars)
+    if trials > cabi.ROUND_MAX_TRIALS:
+        raise ValueError(f"at most {cabi.ROUND_MAX_TRIALS} trials per call")
+    modes = [mode] * len(vars) if isinstance(mode, (str, int)) else list(mode)
+    modes = [ROUNDING_MODES[m] if isinstance(m, str) else int(m) for m in modes]
+    if not (len(vars) == len(As) == len(rngs) == len(modes)):
+        raise ValueError("vars, As, rngs (and mode, when it is a sequence) must have the same length")
+    if not vars:
+        return []
+    reqs = []
+    for v, A, rng, m in zip(vars, As, rngs, modes):
+        v.round_set_graph(A)
+        reqs.append((m, trials, _gauss(rng, trials, v.r)))
+    if loop:
+        if routes is not None:
+            routes[:] = [0] * len(vars)
+        out = []
+        for v, q in zip(vars, reqs):
+            cuts, best, _, _ = v.round(*q)
+            out.append(float(cuts[best]))
+        return out
+    res = cabi.batch_round(abi if abi is not None else vars[0].abi, vars, reqs)
+    if routes is not None:
+        routes[:] = [None if isinstance(x, Exception) else x[4] for x in res]
+    return [x if isinstance(x, Exception) else float(x[0][x[1]]) for x in res]
