@@ -54,6 +54,9 @@ def main():
                     help="the reference runner's rounding callback after every solve (exps/test.jl:132; MaxCut and "
                          "MinimumBisection): on the device — lockstep: one sdplr_hip_batch_round for the whole batch — or with "
                          "the rounding.py callbacks on the downloaded factor; adds `callback_res` to the result")
+    ap.add_argument("--dimacs", action="store_true",
+                    help="eval_DIMACS_errs: every solve ends with the reference's quality certificate (DIMACS_errors, "
+                         "src/coreop.jl:417-453); lockstep: the batch's eigensolves are one sdplr_hip_batch_S_eigval")
     args = ap.parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # launcher: before this process touches torch or the HIP library (see bench.py)
@@ -64,7 +67,7 @@ def main():
             port = so.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus)]
-        cmd += ["--passes", str(args.passes), "--rounding", args.rounding]
+        cmd += ["--passes", str(args.passes), "--rounding", args.rounding] + (["--dimacs"] if args.dimacs else [])
         if args.batch:
             cmd += ["--batch", args.batch]
         sys.exit(subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))))
@@ -119,12 +122,15 @@ def main():
         t0 = time.perf_counter()
         local = batch.solve_local(datas, rank, world, e0["rank"], concurrency=conc, lockstep=lockstep,
                                   ptol=e0["ptol"], objtol=e0["objtol"], seed=e0["seed"], prior_trace_bound=tb,
+                                  **({"eval_DIMACS_errs": True} if args.dimacs else {}),
                                   **({} if rnd is None else dict(rounding=rnd, rounding_on=args.rounding)))
         res = batch.gather(local, len(graphs), dist, device)
         walls.append(time.perf_counter() - t0)
     dt = walls[-1]
     if rank == 0:
         extra = {} if args.rounding == "none" else {"rounding": args.rounding, "callback_res": [float(x) for x in res[:, 5]]}
+        if args.dimacs:
+            extra["dimacs"] = True
         print(json.dumps({"instances": len(graphs), "n_gpus": world, "wall_s": dt, "first_pass_wall_s": walls[0],
                           "problem_build_s": build_s,
                           "mode": "lockstep" if lockstep else "threads", "in_flight_per_gpu": conc, "instances_per_s": len(graphs) / dt,

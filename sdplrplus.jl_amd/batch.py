@@ -13,7 +13,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import cabi
-from .sdplr import _ASCII_ALIASES, REQ_DUAL, REQ_FG, REQ_MAJOR, build_solver, sdplr, sdplr_steps, serve
+from .sdplr import _ASCII_ALIASES, REQ_DUAL, REQ_EIG, REQ_FG, REQ_MAJOR, build_solver, sdplr, sdplr_steps, serve
 from .structs import BurerMonteiroConfig
 
 N_FIELDS = 5  # index, obj, max_dual_value, iter, seconds
@@ -159,7 +159,11 @@ def serve_batch(abi, solvers, reqs) -> list:
     → per instance what ``sdplr.serve`` returns, or the exception its call raised."""
     out = [None] * len(solvers)
     jobs = []
-    for kind, call in ((REQ_MAJOR, cabi.batch_major_iteration), (REQ_DUAL, cabi.batch_dual_obj), (REQ_FG, cabi.batch_fg)):
+    kinds = [(REQ_MAJOR, cabi.batch_major_iteration), (REQ_DUAL, cabi.batch_dual_obj), (REQ_FG, cabi.batch_fg)]
+    if getattr(abi, "has_eig_batch", False):     # (an ABI without the entry point: one by one, below)
+        kinds.append((REQ_EIG, lambda abi_, svs, args: [r_ if isinstance(r_, Exception) else r_[:3]
+                                                         for r_ in cabi.batch_S_eigval(abi_, svs, args)]))
+    for kind, call in kinds:
         ks = [k for k, q in enumerate(reqs) if q[0] == kind]
         if ks:
             jobs.append((ks, call))
@@ -207,7 +211,14 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
     (``rounding.batch_rounding_device``: ``rounding_trials`` draws from each instance's ``rng``), and each result gets
     ``callback_res`` — what ``sdplr(..., callback=)`` with the ``*_rounding_device`` callback returns, bit for bit — and
     ``callback_time`` (the wall of the batch's one call).  An instance whose solve failed keeps its exception and is left
-    out.  Iterations, objective, R and λ do not depend on it."""
+    out.  Iterations, objective, R and λ do not depend on it.
+
+    ``eval_DIMACS_errs=True`` (off by default: nothing changes then): the certificate is each solve's last device step, and
+    its eigensolve is a request like the others (``REQ_EIG``).  An instance that has reached it waits until every live
+    instance is finished or waiting on it too; the eigensolves of the whole batch are then ONE ``cabi.batch_S_eigval`` (an
+    ABI without that entry point serves them one by one).  The shared launch sums in another order than
+    ``sdplr_hip_S_eigval``, so ``DIMACS_errs[3]`` may differ from the one-by-one solve's by eigenvalue round-off; the other
+    five entries and everything else stay bit for bit."""
     abi = abi if abi is not None else cabi.load_hip()
 
     def config_of():
@@ -303,6 +314,14 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
                 if not pending:
                     continue
             ks = sorted(pending)
+            # the certificate (eval_DIMACS_errs) is each solve's last device step: an instance that has reached it waits
+            # until every live instance is there too, and the whole batch's eigensolves go out as ONE call
+            others = [k for k in ks if pending[k][0] != REQ_EIG]
+            if others:
+                ks = others
+            elif waiting:     # (handles still being set up will get there as well)
+                admit(list(wait(list(waiting), return_when=FIRST_COMPLETED).done))
+                continue
             reqs = [cap.outgoing(k, pending[k]) for k in ks]
             for k, response in zip(ks, serve_batch(abi, [solvers[k] for k in ks], reqs)):
                 response = cap.incoming(k, response)

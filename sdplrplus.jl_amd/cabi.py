@@ -144,6 +144,20 @@ ROUND_BATCH_SIGNATURES = {
 ROUND_ROUTE_SINGLE, ROUND_ROUTE_SHARED = 0, 1
 
 
+class EigItem(C.Structure):           # sdplr_hip_eig_item
+    _fields_ = [("s", _vp), ("nev", _i64), ("which", _i32), ("ncv", _i64), ("tol", _f64), ("maxiter", _i64),
+                ("v0", _pf64), ("evals", _pf64), ("n_matvec", _i64), ("n_converged", _i64), ("route", _i32),
+                ("status", _i32)]
+
+
+# include/sdplr_hip_eig_batch.h (S_eigval of a whole batch in one call), checked against that header by
+# tests/test_eig_batch_cabi.py.  An extension on top of sdplr_hip.h, bound only when the library exports it.
+EIG_BATCH_SIGNATURES = {
+    "batch_S_eigval": [_i32, C.POINTER(EigItem)],
+}
+EIG_ROUTE_SINGLE, EIG_ROUTE_SHARED = 0, 1
+
+
 class SdplrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[{code}] {msg}")
@@ -176,6 +190,13 @@ class CABI:
         self.has_round_batch = self.has_round and all(hasattr(self.lib, prefix + name) for name in ROUND_BATCH_SIGNATURES)
         if self.has_round_batch:
             for name, argtypes in ROUND_BATCH_SIGNATURES.items():
+                fn = getattr(self.lib, prefix + name)
+                fn.argtypes = argtypes
+                fn.restype = _i32
+                setattr(self, name, fn)
+        self.has_eig_batch = all(hasattr(self.lib, prefix + name) for name in EIG_BATCH_SIGNATURES)
+        if self.has_eig_batch:
+            for name, argtypes in EIG_BATCH_SIGNATURES.items():
                 fn = getattr(self.lib, prefix + name)
                 fn.argtypes = argtypes
                 fn.restype = _i32
@@ -706,3 +727,31 @@ def batch_round(abi: CABI, solvers, requests):
         _, cuts, xb, lab, trials = keep[k]
         res.append((cuts[:trials], int(arr[k].best), xb, (lab[:trials] if lab is not None else None), int(arr[k].route)))
     return res
+
+
+def batch_S_eigval(abi: CABI, solvers, requests):
+    """``S_eigval`` of every solver in one call (include/sdplr_hip_eig_batch.h); requests[k] =
+    (nev, which, ncv, tol, maxiter, v0) with the meanings of ``DeviceSolver.S_eigval``.
+    → per solver (eigenvalues[nev], matvecs, converged count, route) — route 1: served by the shared launch, 0: by the
+    single-instance call — or the SdplrError its own call would have raised."""
+    if not getattr(abi, "has_eig_batch", False):
+        raise NotImplementedError(f"{abi.path} does not export the batch eigenvalue entry point")
+    arr = (EigItem * len(solvers))()
+    keep = []
+    for k, (sv, q) in enumerate(zip(solvers, requests)):
+        nev, which, ncv, tol, maxiter, v0 = q
+        v0c = _f64c(v0) if v0 is not None else None
+        if v0c is not None and v0c.size != sv.n:
+            raise ValueError(f"v0 of item {k} must have length n = {sv.n}")
+        out = np.zeros(max(int(nev), 1))
+        keep.append((v0c, out, int(nev)))
+        it = arr[k]
+        it.s = sv._h.value
+        it.nev, it.which, it.ncv, it.tol, it.maxiter = int(nev), {"SA": 0, "LA": 1}[which], int(ncv), float(tol), int(maxiter)
+        it.v0 = _pd(v0c) if v0c is not None else None
+        it.evals = _pd(out)
+    rc = abi.batch_S_eigval(len(solvers), arr)
+    out = _batch_results(abi, arr, solvers, lambda q: q, rc)
+    return [o if isinstance(o, Exception) else
+            (keep[k][1][:keep[k][2]], int(arr[k].n_matvec), int(arr[k].n_converged), int(arr[k].route))
+            for k, o in enumerate(out)]

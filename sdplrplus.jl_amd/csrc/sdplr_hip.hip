@@ -4,6 +4,7 @@
 #include "../../include/sdplr_hip.h"
 #include "../../include/sdplr_hip_round.h"
 #include "../../include/sdplr_hip_round_batch.h"
+#include "../../include/sdplr_hip_eig_batch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -35,6 +36,7 @@
 #include "k_group.h"
 #include "k_round.h"
 #include "k_round_batch.h"
+#include "k_eig_resident.h"
 
 namespace {
 
@@ -5427,6 +5429,163 @@ int32_t sdplr_hip_batch_round(int32_t count, sdplr_hip_round_item* it) {
     sdplr_hip_round_item& q = it[i];
     if (!q.s) { q.status = SDPLR_ERR_INVALID_ARG; return; }
     q.status = sdplr_hip_round(q.s, q.mode, q.slot, q.trials, q.gauss, q.cuts, &q.best, q.x_best, q.labels);
+  });
+  for (int i = 0; i < count; i++) if (it[i].status) return it[i].status;
+  return SDPLR_OK;
+}
+
+}  // extern "C"
+
+// ---- the eigenvalue certificate of a whole batch (include/sdplr_hip_eig_batch.h, k_eig_resident.h) -----------------------
+// Per item the preparation of sdplr_hip_S_eigval (NEED_FINAL_RW, ensure_S); beyond it no solver state is written.  The shared
+// grid runs on the first taken handle's stream and reads the other handles' S and y with no event dependency:
+// batch_round_trip's invariant covers it, and an S that ensure_S had to assemble is waited for before the launch.
+namespace {
+constexpr long long SDPLR_EIG_BATCH_NMAX = 2048;   // (beyond it one CU's L2 bandwidth loses to the multi-launch form's 256 CUs)
+struct EigBatchRow {
+  int item, m;
+  bool ylds;
+  size_t v0_off, st_off, V_off, Y_off;   // bytes into the call's device block
+};
+int eig_batch_prepare(S* s) {
+  NEED_FINAL_RW(s);
+  ensure_S(s);
+  HIPCK(s, hipStreamSynchronize(s->stream));   // (the grid runs on another handle's stream)
+  return SDPLR_OK;
+}
+int eig_batch_cycles() {   // restart cycles per launch and instance: a compile-time default, an environment override, nothing else
+  int cap = SDPLR_EIG_RS_CYCLES;
+  if (const char* e = getenv("SDPLR_HIP_BATCH_EIG_CYCLES")) cap = atoi(e);
+  return std::max(1, std::min(cap, 1 << 20));
+}
+int eig_batch_shared(sdplr_hip_eig_item* it, std::vector<EigBatchRow>& rows) {
+  S* s = it[rows[0].item].s;   // the leader: its stream carries the launches, its pool lends the scratch
+  const size_t B = rows.size();
+  const int cap = eig_batch_cycles();
+  const double eps = std::numeric_limits<double>::epsilon();
+  size_t off = batch_up(B * sizeof(EigResArgs)), lds = 0;
+  for (EigBatchRow& q : rows) {
+    const S* sk = it[q.item].s;
+    q.v0_off = off; off += batch_up((size_t)sk->n * sizeof(double));
+    lds = std::max(lds, (size_t)eig_rs_lds_doubles(sk->n, q.m, q.ylds) * sizeof(double));
+  }
+  const size_t st_beg = off;
+  for (EigBatchRow& q : rows) { q.st_off = off; off += batch_up((size_t)(EIG_ST_THETA + q.m + it[q.item].nev + 2) * sizeof(double)); }
+  const size_t tab_bytes = off;   // what goes up: arguments, start vectors, zeroed state and result blocks
+  for (EigBatchRow& q : rows) {
+    const S* sk = it[q.item].s;
+    const size_t ldv = (size_t)(sk->n + 31) / 32 * 32;
+    q.V_off = off; off += batch_up(2 * (size_t)(q.m + 1) * ldv * sizeof(double));
+    q.Y_off = off; off += q.ylds ? 0 : batch_up((size_t)q.m * q.m * sizeof(double));
+  }
+  char* dev = nullptr;
+  int rc = dalloc(s, &dev, off);
+  if (rc) return rc;
+  struct Free { S* s; char* p; ~Free() { dfree(s, p); } } dev_free{s, dev};
+  std::vector<char> tab(tab_bytes, 0);
+  EigResArgs* args = reinterpret_cast<EigResArgs*>(tab.data());
+  for (size_t k = 0; k < B; k++) {
+    const EigBatchRow& q = rows[k];
+    const sdplr_hip_eig_item& x = it[q.item];
+    const S* sk = x.s;
+    const long long n = sk->n, ldv = (n + 31) / 32 * 32;
+    EigResArgs a{};
+    a.n = (int)n; a.m = q.m; a.nev = (int)x.nev; a.which = x.which; a.ylds = q.ylds ? 1 : 0; a.cap = cap;
+    a.maxiter = x.maxiter; a.ldv = ldv;
+    a.tol = x.tol > 0 ? x.tol : eps;                       // ARPACK: tol = 0 ⇒ machine precision
+    a.eps23 = std::pow(eps, 2.0 / 3.0);
+    a.colptr = sk->sp.colptr; a.rowval = sk->sp.rowval; a.nzval = sk->sp.nzval;
+    a.lr = sk->lr; a.yvec = sk->y;
+    a.v0 = reinterpret_cast<const double*>(dev + q.v0_off);
+    a.V[0] = reinterpret_cast<double*>(dev + q.V_off);
+    a.V[1] = a.V[0] + (size_t)(q.m + 1) * ldv;
+    a.Yg = q.ylds ? nullptr : reinterpret_cast<double*>(dev + q.Y_off);
+    a.state = reinterpret_cast<double*>(dev + q.st_off);
+    a.out = a.state + EIG_ST_THETA + q.m;
+    args[k] = a;
+    double* st = reinterpret_cast<double*>(tab.data() + q.v0_off);   // the caller's start vector, or sdplr_hip_S_eigval's fixed one
+    if (x.v0) std::copy(x.v0, x.v0 + n, st);
+    else { unsigned long long z = 0x9E3779B97F4A7C15ull; for (long long i = 0; i < n; i++) { z = z * 6364136223846793005ull + 1442695040888963407ull; st[i] = (double)(z >> 11) / 9007199254740992.0 - 0.5; } }
+  }
+  if ((rc = h2d_copy(s, dev, tab.data(), tab_bytes))) return rc;
+  std::vector<char> res(tab_bytes - st_beg);
+  RS_SET_ATTR(k_eig_resident_batch);
+  // every launch runs ≤ cap cycles of each unfinished instance; a finished one leaves its block at once
+  long long most = 1;
+  for (const EigBatchRow& q : rows) most = std::max<long long>(most, (long long)((it[q.item].maxiter + cap - 1) / cap));
+  bool all_done = false;
+  for (long long launch = 0; launch <= most && !all_done; launch++) {
+    k_eig_resident_batch<<<(unsigned int)B, SDPLR_RS_NT, lds, s->stream>>>(reinterpret_cast<const EigResArgs*>(dev));
+    HIPCK(s, hipGetLastError());
+    HIPCK(s, hipMemcpyAsync(res.data(), dev + st_beg, res.size(), hipMemcpyDeviceToHost, s->stream));
+    HIPCK(s, hipStreamSynchronize(s->stream));
+    all_done = true;
+    for (const EigBatchRow& q : rows)
+      all_done = all_done && reinterpret_cast<const double*>(res.data() + (q.st_off - st_beg))[EIG_ST_DONE] != 0.0;
+  }
+  if (!all_done) return fail(s, SDPLR_ERR_HIP, "batch_S_eigval: an instance did not finish within its cycle budget");
+  for (const EigBatchRow& q : rows) {
+    sdplr_hip_eig_item& x = it[q.item];
+    const double* o = reinterpret_cast<const double*>(res.data() + (q.st_off - st_beg)) + EIG_ST_THETA + q.m;
+    for (int64_t i = 0; i < x.nev; i++) x.evals[i] = o[i];
+    x.n_matvec = (int64_t)o[x.nev];
+    x.n_converged = (int64_t)o[x.nev + 1];
+  }
+  return SDPLR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t sdplr_hip_batch_S_eigval(int32_t count, sdplr_hip_eig_item* it) {
+  if (count < 0 || (count > 0 && !it)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_S_eigval: bad args");
+  if (have_device() <= 0) return fail(nullptr, SDPLR_ERR_NO_DEVICE, "no usable HIP device (libsdplr_hip has no CPU fallback)");
+  std::vector<int> single;
+  {
+    std::vector<const S*> hs;
+    for (int i = 0; i < count; i++) hs.push_back(it[i].s);
+    if (!batch_handles_distinct(hs)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_S_eigval: a handle appears twice");   // (before any handle is dereferenced or any item written)
+    int dev = -1;
+    if (!batch_one_device(hs, &dev)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_S_eigval: the handles live on different devices");
+    for (int i = 0; i < count; i++) { it[i].status = SDPLR_ERR_UNSERVED; it[i].route = 0; }
+    ApiShared api_guard(dev);
+    long long nmax = SDPLR_EIG_BATCH_NMAX;
+    if (const char* e = getenv("SDPLR_HIP_BATCH_EIG_NMAX")) nmax = std::max(0LL, std::min(nmax, atoll(e)));
+    const char* off_env = getenv("SDPLR_HIP_NO_BATCH_EIG");
+    const bool off = off_env != nullptr && atoi(off_env) != 0;
+    std::vector<EigBatchRow> rows;
+    for (int i = 0; i < count; i++) {
+      const sdplr_hip_eig_item& q = it[i];
+      S* s = q.s;
+      // whatever sdplr_hip_S_eigval would refuse goes to that call, which reports the item's status
+      bool ok = !off && s && s->finalized && q.evals && q.nev >= 1 && q.nev <= s->n && (q.which == 0 || q.which == 1) && q.maxiter >= 1 &&
+                rs_route_open(s) && s->have_sparse && s->lr.ST <= SDPLR_LRMAX && s->n <= nmax;
+      int m = 0;
+      bool ylds = false;
+      if (ok) {   // sdplr_hip_S_eigval's basis size
+        const int64_t n = s->n;
+        m = (int)std::min<int64_t>(n, std::max<int64_t>(q.ncv > 0 ? q.ncv : 100, std::min<int64_t>(n, 2 * q.nev + 1)));
+        if (m > 256) m = 256;
+        ok = q.nev <= m && (size_t)eig_rs_lds_doubles(n, m, false) * sizeof(double) <= RS_LDS_MAX;
+        ylds = ok && (size_t)eig_rs_lds_doubles(n, m, true) * sizeof(double) <= RS_LDS_MAX;
+      }
+      if (!ok || eig_batch_prepare(s) != SDPLR_OK) { single.push_back(i); continue; }
+      rows.push_back(EigBatchRow{i, m, ylds, 0, 0, 0, 0});
+    }
+    if (!rows.empty()) {
+      const int rc = eig_batch_shared(it, rows);
+      S* lead = it[rows[0].item].s;
+      for (const EigBatchRow& q : rows) {
+        sdplr_hip_eig_item& x = it[q.item];
+        x.status = rc;
+        x.route = 1;
+        if (rc && x.s != lead) x.s->err = lead->err;
+      }
+    }
+  }
+  run_singles(single, [&](int i) {
+    sdplr_hip_eig_item& q = it[i];
+    q.status = sdplr_hip_S_eigval(q.s, q.nev, q.which, q.ncv, q.tol, q.maxiter, q.v0, q.evals, &q.n_matvec, &q.n_converged);
   });
   for (int i = 0; i < count; i++) if (it[i].status) return it[i].status;
   return SDPLR_OK;

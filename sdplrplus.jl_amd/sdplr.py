@@ -100,6 +100,19 @@ def SDP_S_eigval(var: DeviceSolver, nevs: int = 1, preprocessed: bool = False, *
 
 def DIMACS_errors(data: SDPData, var: DeviceSolver) -> np.ndarray:
     """The six DIMACS errors (src/coreop.jl:417-453) with X = RRᵀ, Z = C − 𝒜*(λ)."""
+    steps = DIMACS_errors_steps(data, var)
+    try:
+        req = next(steps)
+        while True:
+            req = steps.send(serve(var, req))
+    except StopIteration as done:
+        return done.value
+
+
+def DIMACS_errors_steps(data: SDPData, var: DeviceSolver):
+    """``DIMACS_errors`` as a generator in the manner of ``sdplr_steps``: the eigensolve of SDP_S_eigval (:436-437) is
+    yielded as a ``REQ_EIG`` request — ``serve`` answers it with ``var.S_eigval``, a lockstep driver with one
+    ``batch_S_eigval`` for every instance waiting on it — everything around it runs here."""
     m = data.m
     pv_raw = var.primal_vio_raw
     normb = float(np.linalg.norm(data.b))
@@ -108,7 +121,11 @@ def DIMACS_errors(data: SDPData, var: DeviceSolver) -> np.ndarray:
     λ = var.λ
     var.y = np.concatenate([-λ, [1.0]])                # copy2y_λ! (:238-246)
     var.At_preprocess()                                # (:436)
-    ev = SDP_S_eigval(var, 1, True, which="SA", ncv=min(100, data.n), maxiter=1000000)
+    # SDP_S_eigval(var, 1, True, which="SA", ncv=min(100, n), maxiter=1000000), its solver call as a request
+    vals, _matvecs, nconv = yield (REQ_EIG, 1, "SA", min(100, data.n), 0.0, 100000, None)
+    if nconv < 1:
+        print(f"Warning: SDP_S_eigval: {nconv} of 1 eigenvalues converged.", file=sys.stderr)
+    ev = np.sort(vals)
     normC = data.normC()
     err4 = max(0.0, -float(ev[0])) / (1.0 + normC)
     obj = var.obj
@@ -132,6 +149,8 @@ def _print_row(config, majoriter, localiter, iter_, L, obj, σ, gtol, ptol, gnor
 # control flow runs one solve (``_sdplr``: every request is served at once on the instance's own handle) or a batch side by
 # side (``batch.solve_lockstep``: the same request of all instances is ONE call, one kernel launch for the whole batch).
 REQ_FG, REQ_MAJOR, REQ_INNER, REQ_DUAL = "fg", "major_iteration", "inner_loop", "dual_obj"
+# … and the eigensolve of DIMACS_errors (eval_DIMACS_errs): (REQ_EIG, nev, which, ncv, tol, maxiter, v0) → (evals, matvecs, nconv)
+REQ_EIG = "S_eigval"
 
 
 def serve(var: DeviceSolver, req: tuple) -> tuple:
@@ -145,6 +164,8 @@ def serve(var: DeviceSolver, req: tuple) -> tuple:
         return var.inner_loop(*args) + (var.obj,)
     if kind == REQ_DUAL:
         return var.dual_obj(*args) + (None,)      # (third: var.y if the driver already has it — the batched call does)
+    if kind == REQ_EIG:
+        return var.S_eigval(*args)
     raise ValueError(kind)
 
 
@@ -342,7 +363,7 @@ def sdplr_steps(data: SDPData, var: DeviceSolver, config: BurerMonteiroConfig, n
     _print_row(config, majoriter, -1, iter_, L_val, obj, σ_now, cur_gtol, cur_ptol, grad_norm,
                primal_vio_norm, min_duality_gap, max_dual_value)
     totaltime = time.time() - starttime
-    DIMACS_errs = DIMACS_errors(data, var) if config.eval_DIMACS_errs else np.zeros(6)   # :419-425
+    DIMACS_errs = (yield from DIMACS_errors_steps(data, var)) if config.eval_DIMACS_errs else np.zeros(6)   # :419-425
     Rt = var.Rt
     return {                                                    # :426-448
         "Rt": Rt, "lambda": best_λ, "Rt0": Rt0, "lambda0": λ0, "sigma": σ_now,
