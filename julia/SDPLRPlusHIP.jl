@@ -17,6 +17,18 @@
 
 const LIBSDPLR_HIP = get(ENV, "LIBSDPLR_HIP", "libsdplr_hip.so")
 
+# Entry points of the extension headers (include/sdplr_hip_dual_hp.h) are not part of include/sdplr_hip.h: they are looked up
+# by name at first use, so that a libsdplr_hip.so built before they existed still loads and serves everything else.  The
+# call below is checked against that header by tests/test_dual_hp_cabi.py.
+import Libdl
+const HIP_DUAL_OBJ_HP = Ref{Ptr{Cvoid}}(C_NULL)
+function hip_dual_obj_hp_ptr()
+    if HIP_DUAL_OBJ_HP[] == C_NULL
+        HIP_DUAL_OBJ_HP[] = Libdl.dlsym(Libdl.dlopen(LIBSDPLR_HIP), :sdplr_hip_dual_obj_hp)
+    end
+    return HIP_DUAL_OBJ_HP[]
+end
+
 # ---- slot ids of include/sdplr_hip.h ---------------------------------------------------------------------------
 const HIP_F_RT = Int32(0)
 const HIP_F_GT = Int32(1)
@@ -288,13 +300,14 @@ end
 
 "dual_obj(data, var, aux, trace_bound, iter; highprecision) — src/coreop.jl:376-415"
 function dual_obj(data, var::SolverVars, aux::HIPAux, trace_bound, iter::Integer; highprecision::Bool=false)
-    b = b_vector(data)
-    m = length(b)
-    if highprecision                                                       # :389-400
-        g!(var, aux)                                                       # leaves y = copy2y_λ_sub_pvio!, S current (:384-385)
-        hip_get_vec!(var.y, aux, HIP_V_Y)
-        evs, _ = SDP_S_eigval(var, aux, 1, true; which=:SA, ncv=min(100, side_dimension(aux)), tol=1e-6, maxiter=1000000)
-        return -dot(view(var.y, 1:m), b) + trace_bound * min(evs[1], 0.0), evs[1]
+    if highprecision                                                       # :384-385, :389-400, :412 as ONE call (sdplr_hip_dual_hp.h)
+        d, e = Ref(0.0), Ref(0.0)
+        mv, nc = Ref{Int64}(0), Ref{Int64}(0)
+        hip_check(ccall(hip_dual_obj_hp_ptr(), Int32,
+                        (Ptr{Cvoid}, Float64, Int64, Float64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+                        aux.handle, trace_bound, min(100, side_dimension(aux)), 1e-6, 100000, C_NULL, d, e, mv, nc), aux.handle)
+        nc[] < 1 && @warn "SDP_S_eigval: $(nc[]) of 1 eigenvalues converged."
+        return d[], e[]
     end
     v0 = randn(side_dimension(aux))
     d, e = Ref(0.0), Ref(0.0)

@@ -13,7 +13,8 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import cabi
-from .sdplr import _ASCII_ALIASES, REQ_DUAL, REQ_EIG, REQ_FG, REQ_MAJOR, build_solver, sdplr, sdplr_steps, serve
+from .sdplr import (_ASCII_ALIASES, REQ_DUAL, REQ_DUAL_HP, REQ_EIG, REQ_FG, REQ_MAJOR, build_solver, sdplr, sdplr_steps, serve,
+                    warn_unconverged)
 from .structs import BurerMonteiroConfig
 
 N_FIELDS = 5  # index, obj, max_dual_value, iter, seconds
@@ -153,6 +154,18 @@ class _Cap:
         return (L, gn, pn, alpha, st[1], why, obj)
 
 
+def _batch_dual_hp(abi, solvers, args) -> list:
+    """The REQ_DUAL_HP requests of a round as ONE ``cabi.batch_dual_obj_hp`` → per instance what ``serve`` answers:
+    (dual_value, mineig, y)."""
+    out = []
+    for r_ in cabi.batch_dual_obj_hp(abi, solvers, args):
+        if not isinstance(r_, Exception):
+            warn_unconverged(r_[3])
+            r_ = (r_[0], r_[1], r_[4])
+        out.append(r_)
+    return out
+
+
 def serve_batch(abi, solvers, reqs) -> list:
     """The pending request of every instance, served side by side: the requests of one kind are ONE library call
     (``sdplr_hip_batch_*``: one kernel launch for all the small instances among them); the rest go one by one.
@@ -163,6 +176,8 @@ def serve_batch(abi, solvers, reqs) -> list:
     if getattr(abi, "has_eig_batch", False):     # (an ABI without the entry point: one by one, below)
         kinds.append((REQ_EIG, lambda abi_, svs, args: [r_ if isinstance(r_, Exception) else r_[:3]
                                                          for r_ in cabi.batch_S_eigval(abi_, svs, args)]))
+    if getattr(abi, "has_dual_hp", False):       # (likewise; ``serve`` then runs the bound from the host)
+        kinds.append((REQ_DUAL_HP, _batch_dual_hp))
     for kind, call in kinds:
         ks = [k for k, q in enumerate(reqs) if q[0] == kind]
         if ks:
@@ -218,7 +233,14 @@ def solve_lockstep(datas: Sequence, r: int, *, abi=None, setup_workers: int = 8,
     instance is finished or waiting on it too; the eigensolves of the whole batch are then ONE ``cabi.batch_S_eigval`` (an
     ABI without that entry point serves them one by one).  The shared launch sums in another order than
     ``sdplr_hip_S_eigval``, so ``DIMACS_errs[3]`` may differ from the one-by-one solve's by eigenvalue round-off; the other
-    five entries and everything else stay bit for bit."""
+    five entries and everything else stay bit for bit.
+
+    ``eigval_highprecision=True`` (off by default: nothing changes then): the dual bound of a major iteration is the request
+    ``REQ_DUAL_HP``, and the bounds of all the instances that wait on one in a round are ONE ``cabi.batch_dual_obj_hp``, beside
+    the round's other calls (an ABI without that entry point serves them one by one).  y and S of each bound are those of
+    the one-by-one solve bit for bit; the eigenvalue comes from the shared launch, so ``max_dual_value`` agrees with the
+    one-by-one solve's to the accuracy of the eigensolver's convergence test (tol = 1e-6), and an instance whose stopping
+    test sits within that of its threshold may take a different number of major iterations."""
     abi = abi if abi is not None else cabi.load_hip()
 
     def config_of():

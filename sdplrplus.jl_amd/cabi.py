@@ -158,6 +158,21 @@ EIG_BATCH_SIGNATURES = {
 EIG_ROUTE_SINGLE, EIG_ROUTE_SHARED = 0, 1
 
 
+class DualHpItem(C.Structure):        # sdplr_hip_dual_hp_item
+    _fields_ = [("s", _vp), ("trace_bound", _f64), ("ncv", _i64), ("tol", _f64), ("maxiter", _i64), ("v0", _pf64),
+                ("y_out", _pf64), ("dual_value", _f64), ("mineig", _f64), ("n_matvec", _i64), ("n_converged", _i64),
+                ("route", _i32), ("status", _i32)]
+
+
+# include/sdplr_hip_dual_hp.h (the high-precision dual bound as one call, and of a whole batch in one call), checked against
+# that header by tests/test_dual_hp_cabi.py.  An extension on top of sdplr_hip.h, bound only when the library exports both.
+DUAL_HP_SIGNATURES = {
+    "dual_obj_hp": [_vp, _f64, _i64, _f64, _i64, _pf64, _pf64, _pf64, _pi64, _pi64],
+    "batch_dual_obj_hp": [_i32, C.POINTER(DualHpItem)],
+}
+DUAL_HP_ROUTE_SINGLE, DUAL_HP_ROUTE_SHARED = 0, 1
+
+
 class SdplrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[{code}] {msg}")
@@ -197,6 +212,13 @@ class CABI:
         self.has_eig_batch = all(hasattr(self.lib, prefix + name) for name in EIG_BATCH_SIGNATURES)
         if self.has_eig_batch:
             for name, argtypes in EIG_BATCH_SIGNATURES.items():
+                fn = getattr(self.lib, prefix + name)
+                fn.argtypes = argtypes
+                fn.restype = _i32
+                setattr(self, name, fn)
+        self.has_dual_hp = all(hasattr(self.lib, prefix + name) for name in DUAL_HP_SIGNATURES)
+        if self.has_dual_hp:
+            for name, argtypes in DUAL_HP_SIGNATURES.items():
                 fn = getattr(self.lib, prefix + name)
                 fn.argtypes = argtypes
                 fn.restype = _i32
@@ -569,6 +591,23 @@ class DeviceSolver:
                                    C.byref(e)))
         return float(d.value), float(e.value)
 
+    def dual_obj_hp(self, trace_bound: float, ncv: int = 0, tol: float = 0.0, maxiter: int = 100000,
+                    v0: Optional[np.ndarray] = None) -> Tuple[float, float, int, int]:
+        """dual_obj(...; highprecision=true)  src/coreop.jl:376-415 (branch :389-400) as one device call
+        (include/sdplr_hip_dual_hp.h): copy2y, 𝒜t_preprocess!, ``S_eigval(1, "SA", ncv, tol, maxiter, v0)`` and the
+        bound → (dual_value, λ_min, matvecs, converged count).  The handle holds y and S of the bound afterwards."""
+        if not getattr(self.abi, "has_dual_hp", False):
+            raise NotImplementedError(f"{self.abi.path} does not export the high-precision dual bound")
+        v0c = _f64c(v0) if v0 is not None else None
+        if v0c is not None and v0c.size != self.n:
+            raise ValueError(f"v0 must have length n = {self.n}")
+        d, e = C.c_double(), C.c_double()
+        mv, nc = C.c_int64(0), C.c_int64(0)
+        self._ck(self.abi.dual_obj_hp(self._h, float(trace_bound), int(ncv), float(tol), int(maxiter),
+                                      _pd(v0c) if v0c is not None else None, C.byref(d), C.byref(e), C.byref(mv),
+                                      C.byref(nc)))
+        return float(d.value), float(e.value), int(mv.value), int(nc.value)
+
     # -- randomized rounding on the device (include/sdplr_hip_round.h) ----------------------------------
     def _need_round(self):
         if not getattr(self.abi, "has_round", False):
@@ -754,4 +793,34 @@ def batch_S_eigval(abi: CABI, solvers, requests):
     out = _batch_results(abi, arr, solvers, lambda q: q, rc)
     return [o if isinstance(o, Exception) else
             (keep[k][1][:keep[k][2]], int(arr[k].n_matvec), int(arr[k].n_converged), int(arr[k].route))
+            for k, o in enumerate(out)]
+
+
+def batch_dual_obj_hp(abi: CABI, solvers, requests):
+    """``dual_obj_hp`` of every solver in one call (include/sdplr_hip_dual_hp.h); requests[k] =
+    (trace_bound, ncv, tol, maxiter, v0) with the meanings of ``DeviceSolver.dual_obj_hp``.
+    → per solver (dual_value, λ_min, matvecs, converged count, y, route) — ``var.y`` as the bound leaves it comes back with
+    the results; route 1: served by the shared launches, 0: by the single-instance call — or the SdplrError its own call
+    would have raised."""
+    if not getattr(abi, "has_dual_hp", False):
+        raise NotImplementedError(f"{abi.path} does not export the high-precision dual bound")
+    arr = (DualHpItem * len(solvers))()
+    keep, ys = [], []
+    for k, (sv, q) in enumerate(zip(solvers, requests)):
+        trace_bound, ncv, tol, maxiter, v0 = q
+        v0c = _f64c(v0) if v0 is not None else None
+        if v0c is not None and v0c.size != sv.n:
+            raise ValueError(f"v0 of item {k} must have length n = {sv.n}")
+        keep.append(v0c)
+        ys.append(np.empty(sv.m + 1))
+        it = arr[k]
+        it.s = sv._h.value
+        it.trace_bound, it.ncv, it.tol, it.maxiter = float(trace_bound), int(ncv), float(tol), int(maxiter)
+        it.v0 = _pd(v0c) if v0c is not None else None
+        it.y_out = _pd(ys[k])
+    rc = abi.batch_dual_obj_hp(len(solvers), arr)
+    out = _batch_results(abi, arr, solvers, lambda q: q, rc)
+    return [o if isinstance(o, Exception) else
+            (float(arr[k].dual_value), float(arr[k].mineig), int(arr[k].n_matvec), int(arr[k].n_converged), ys[k],
+             int(arr[k].route))
             for k, o in enumerate(out)]

@@ -5,6 +5,7 @@
 #include "../../include/sdplr_hip_round.h"
 #include "../../include/sdplr_hip_round_batch.h"
 #include "../../include/sdplr_hip_eig_batch.h"
+#include "../../include/sdplr_hip_dual_hp.h"
 
 #include <hip/hip_runtime.h>
 
@@ -37,6 +38,7 @@
 #include "k_round.h"
 #include "k_round_batch.h"
 #include "k_eig_resident.h"
+#include "k_dual_hp.h"
 
 namespace {
 
@@ -4362,14 +4364,18 @@ void jacobi_eigh(std::vector<double>& A, int m, std::vector<double>& w, std::vec
 }  // namespace
 extern "C" {
 
-// SDP_S_eigval, src/coreop.jl:351-374 — see include/sdplr_hip.h
-int32_t sdplr_hip_S_eigval(S* s, int64_t nev, int32_t which, int64_t ncv_in, double tol, int64_t maxiter,
-                           const double* v0, double* evals, int64_t* n_matvec, int64_t* n_converged) {
-  ApiShared api_guard(dev_of(s));
-  NEED_FINAL_RW(s);
-  const int64_t n = s->n;
-  if (!evals || nev < 1 || nev > n || (which != 0 && which != 1) || maxiter < 1)
+// the argument test of sdplr_hip_S_eigval (and of sdplr_hip_dual_obj_hp, before it writes y)
+static int32_t S_eigval_check(S* s, int64_t nev, int32_t which, int64_t maxiter, const double* evals) {
+  if (!evals || nev < 1 || nev > s->n || (which != 0 && which != 1) || maxiter < 1)
     return fail(s, SDPLR_ERR_INVALID_ARG, "S_eigval: bad args");
+  return SDPLR_OK;
+}
+// SDP_S_eigval, src/coreop.jl:351-374, behind the entry point's lock and NEED_FINAL_RW: the body of sdplr_hip_S_eigval
+// and of the eigensolve of sdplr_hip_dual_obj_hp
+static int32_t S_eigval_run(S* s, int64_t nev, int32_t which, int64_t ncv_in, double tol, int64_t maxiter,
+                            const double* v0, double* evals, int64_t* n_matvec, int64_t* n_converged) {
+  if (int rc_a = S_eigval_check(s, nev, which, maxiter, evals)) return rc_a;
+  const int64_t n = s->n;
   ensure_S(s);
   int m = (int)std::min<int64_t>(n, std::max<int64_t>(ncv_in > 0 ? ncv_in : 100, std::min<int64_t>(n, 2 * nev + 1)));
   if (m > 256) m = 256;
@@ -4469,6 +4475,35 @@ int32_t sdplr_hip_S_eigval(S* s, int64_t nev, int32_t which, int64_t ncv_in, dou
   rc = sync_check(s);
   cleanup();
   return rc;
+}
+
+// SDP_S_eigval, src/coreop.jl:351-374 — see include/sdplr_hip.h
+int32_t sdplr_hip_S_eigval(S* s, int64_t nev, int32_t which, int64_t ncv_in, double tol, int64_t maxiter,
+                           const double* v0, double* evals, int64_t* n_matvec, int64_t* n_converged) {
+  ApiShared api_guard(dev_of(s));
+  NEED_FINAL_RW(s);
+  return S_eigval_run(s, nev, which, ncv_in, tol, maxiter, v0, evals, n_matvec, n_converged);
+}
+
+// dual_obj(...; highprecision=true), src/coreop.jl:376-415 — see include/sdplr_hip_dual_hp.h
+int32_t sdplr_hip_dual_obj_hp(S* s, double trace_bound, int64_t ncv, double tol, int64_t maxiter, const double* v0,
+                              double* dual_value, double* mineig, int64_t* n_matvec, int64_t* n_converged) {
+  if (have_device() <= 0) return fail(nullptr, SDPLR_ERR_NO_DEVICE, "no usable HIP device (libsdplr_hip has no CPU fallback)");
+  ApiShared api_guard(dev_of(s));
+  NEED_FINAL_RW(s);
+  double ev = 0.0;
+  int rc = S_eigval_check(s, 1, 0, maxiter, &ev);   // (before y is written)
+  if (rc) return rc;
+  enq_copy2y(s, 0);            // :384
+  enq_At_preprocess(s, 0);     // :385
+  s->S_stale = false;
+  if ((rc = S_eigval_run(s, 1, 0, ncv, tol, maxiter, v0, &ev, n_matvec, n_converged))) return rc;   // :389-400
+  k_dot<<<s->nb_m, SDPLR_NT, 0, s->stream>>>((int)s->m, s->y, s->b, SLOT_DUALYB, s->partials);
+  k_reduce_slot<<<1, SDPLR_NT, 0, s->stream>>>(&s->ctrl->descent, SLOT_DUALYB, s->nb_m, s->partials);
+  if ((rc = pull(s))) return rc;
+  if (dual_value) *dual_value = -s->hc->descent + trace_bound * std::min(ev, 0.0);   // :412
+  if (mineig) *mineig = ev;
+  return sync_check(s);
 }
 
 // dot of two factor-shaped arrays on the device (err6 = dot(Rt, Rt·S), src/coreop.jl:449)
@@ -5436,17 +5471,59 @@ int32_t sdplr_hip_batch_round(int32_t count, sdplr_hip_round_item* it) {
 
 }  // extern "C"
 
-// ---- the eigenvalue certificate of a whole batch (include/sdplr_hip_eig_batch.h, k_eig_resident.h) -----------------------
+// ---- the eigenvalue certificate of a whole batch (include/sdplr_hip_eig_batch.h, k_eig_resident.h) and the high-precision
+// dual bound of a whole batch (include/sdplr_hip_dual_hp.h, k_dual_hp.h) -------------------------------------------------
 // Per item the preparation of sdplr_hip_S_eigval (NEED_FINAL_RW, ensure_S); beyond it no solver state is written.  The shared
 // grid runs on the first taken handle's stream and reads the other handles' S and y with no event dependency:
 // batch_round_trip's invariant covers it, and an S that ensure_S had to assemble is waited for before the launch.
+// The dual bound's rows need no preparation on their own streams: the prologue grid (k_dual_hp_prologue) writes y and S of
+// every row on the leader's stream, ahead of the eigensolver's launches; its argument table goes up with theirs and its
+// ⟨y, b⟩ (and the copies of y asked for) come back with their results.
 namespace {
 constexpr long long SDPLR_EIG_BATCH_NMAX = 2048;   // (beyond it one CU's L2 bandwidth loses to the multi-launch form's 256 CUs)
 struct EigBatchRow {
   int item, m;
   bool ylds;
-  size_t v0_off, st_off, V_off, Y_off;   // bytes into the call's device block
+  // the request: sdplr_hip_S_eigval's arguments, and where its results go
+  S* s;
+  int64_t nev;
+  int32_t which;
+  double tol;
+  int64_t maxiter;
+  const double* v0;
+  double* evals;
+  int64_t *n_matvec, *n_converged;
+  // the dual bound (sdplr_hip_batch_dual_obj_hp): the prologue's ⟨y[1:m], b⟩, and y itself if the item asks for it
+  double* yb;
+  double* y_out;
+  size_t v0_off, st_off, y_off, V_off, Y_off;   // bytes into the call's device block
 };
+// environment of the two batch calls (read per call): the switch and the largest n of the shared launch
+struct EigBatchEnv {
+  bool off;
+  long long nmax;
+  EigBatchEnv() {
+    nmax = SDPLR_EIG_BATCH_NMAX;
+    if (const char* e = getenv("SDPLR_HIP_BATCH_EIG_NMAX")) nmax = std::max(0LL, std::min(nmax, atoll(e)));
+    const char* off_env = getenv("SDPLR_HIP_NO_BATCH_EIG");
+    off = off_env != nullptr && atoi(off_env) != 0;
+  }
+};
+// does the shared launch take this request?  Whatever sdplr_hip_S_eigval would refuse goes to the single-instance call,
+// which reports the item's status.  → the basis size and where the projected eigenvectors live
+bool eig_batch_takes(const EigBatchEnv& env, const S* s, int64_t nev, int32_t which, int64_t ncv, int64_t maxiter,
+                     bool have_evals, int* m_out, bool* ylds_out) {
+  bool ok = !env.off && s && s->finalized && have_evals && nev >= 1 && nev <= s->n && (which == 0 || which == 1) && maxiter >= 1 &&
+            rs_route_open(s) && s->have_sparse && s->lr.ST <= SDPLR_LRMAX && s->n <= env.nmax;
+  if (!ok) return false;
+  const int64_t n = s->n;   // sdplr_hip_S_eigval's basis size
+  int m = (int)std::min<int64_t>(n, std::max<int64_t>(ncv > 0 ? ncv : 100, std::min<int64_t>(n, 2 * nev + 1)));
+  if (m > 256) m = 256;
+  ok = nev <= m && (size_t)eig_rs_lds_doubles(n, m, false) * sizeof(double) <= RS_LDS_MAX;
+  *m_out = m;
+  *ylds_out = ok && (size_t)eig_rs_lds_doubles(n, m, true) * sizeof(double) <= RS_LDS_MAX;
+  return ok;
+}
 int eig_batch_prepare(S* s) {
   NEED_FINAL_RW(s);
   ensure_S(s);
@@ -5458,22 +5535,27 @@ int eig_batch_cycles() {   // restart cycles per launch and instance: a compile-
   if (const char* e = getenv("SDPLR_HIP_BATCH_EIG_CYCLES")) cap = atoi(e);
   return std::max(1, std::min(cap, 1 << 20));
 }
-int eig_batch_shared(sdplr_hip_eig_item* it, std::vector<EigBatchRow>& rows) {
-  S* s = it[rows[0].item].s;   // the leader: its stream carries the launches, its pool lends the scratch
+// `dual`: every row is a dual bound — the prologue grid runs first, and each result block carries ⟨y, b⟩ behind the
+// eigensolver's own numbers
+int eig_batch_shared(std::vector<EigBatchRow>& rows, bool dual) {
+  S* s = rows[0].s;   // the leader: its stream carries the launches, its pool lends the scratch
   const size_t B = rows.size();
   const int cap = eig_batch_cycles();
   const double eps = std::numeric_limits<double>::epsilon();
-  size_t off = batch_up(B * sizeof(EigResArgs)), lds = 0;
+  const size_t dh_off = batch_up(B * sizeof(EigResArgs));
+  size_t off = dh_off + (dual ? batch_up(B * sizeof(DualHpArgs)) : 0), lds = 0;
   for (EigBatchRow& q : rows) {
-    const S* sk = it[q.item].s;
+    const S* sk = q.s;
     q.v0_off = off; off += batch_up((size_t)sk->n * sizeof(double));
     lds = std::max(lds, (size_t)eig_rs_lds_doubles(sk->n, q.m, q.ylds) * sizeof(double));
   }
   const size_t st_beg = off;
-  for (EigBatchRow& q : rows) { q.st_off = off; off += batch_up((size_t)(EIG_ST_THETA + q.m + it[q.item].nev + 2) * sizeof(double)); }
+  for (EigBatchRow& q : rows) { q.st_off = off; off += batch_up((size_t)(EIG_ST_THETA + q.m + q.nev + 2 + (dual ? 1 : 0)) * sizeof(double)); }
   const size_t tab_bytes = off;   // what goes up: arguments, start vectors, zeroed state and result blocks
+  for (EigBatchRow& q : rows) { q.y_off = off; off += q.y_out ? batch_up((size_t)(q.s->m + 1) * sizeof(double)) : 0; }
+  const size_t res_end = off;     // what comes back: the state and result blocks, and the copies of y behind them
   for (EigBatchRow& q : rows) {
-    const S* sk = it[q.item].s;
+    const S* sk = q.s;
     const size_t ldv = (size_t)(sk->n + 31) / 32 * 32;
     q.V_off = off; off += batch_up(2 * (size_t)(q.m + 1) * ldv * sizeof(double));
     q.Y_off = off; off += q.ylds ? 0 : batch_up((size_t)q.m * q.m * sizeof(double));
@@ -5484,15 +5566,15 @@ int eig_batch_shared(sdplr_hip_eig_item* it, std::vector<EigBatchRow>& rows) {
   struct Free { S* s; char* p; ~Free() { dfree(s, p); } } dev_free{s, dev};
   std::vector<char> tab(tab_bytes, 0);
   EigResArgs* args = reinterpret_cast<EigResArgs*>(tab.data());
+  DualHpArgs* dargs = reinterpret_cast<DualHpArgs*>(tab.data() + dh_off);
   for (size_t k = 0; k < B; k++) {
     const EigBatchRow& q = rows[k];
-    const sdplr_hip_eig_item& x = it[q.item];
-    const S* sk = x.s;
+    const S* sk = q.s;
     const long long n = sk->n, ldv = (n + 31) / 32 * 32;
     EigResArgs a{};
-    a.n = (int)n; a.m = q.m; a.nev = (int)x.nev; a.which = x.which; a.ylds = q.ylds ? 1 : 0; a.cap = cap;
-    a.maxiter = x.maxiter; a.ldv = ldv;
-    a.tol = x.tol > 0 ? x.tol : eps;                       // ARPACK: tol = 0 ⇒ machine precision
+    a.n = (int)n; a.m = q.m; a.nev = (int)q.nev; a.which = q.which; a.ylds = q.ylds ? 1 : 0; a.cap = cap;
+    a.maxiter = q.maxiter; a.ldv = ldv;
+    a.tol = q.tol > 0 ? q.tol : eps;                       // ARPACK: tol = 0 ⇒ machine precision
     a.eps23 = std::pow(eps, 2.0 / 3.0);
     a.colptr = sk->sp.colptr; a.rowval = sk->sp.rowval; a.nzval = sk->sp.nzval;
     a.lr = sk->lr; a.yvec = sk->y;
@@ -5503,16 +5585,31 @@ int eig_batch_shared(sdplr_hip_eig_item* it, std::vector<EigBatchRow>& rows) {
     a.state = reinterpret_cast<double*>(dev + q.st_off);
     a.out = a.state + EIG_ST_THETA + q.m;
     args[k] = a;
+    if (dual) {
+      DualHpArgs d{};
+      d.m = (int)sk->m; d.n_sparse = (int)sk->n_sparse; d.nnzT = sk->sp.nnzT; d.nnzS = sk->sp.nnzS;
+      d.c = sk->ctrl;
+      d.lam = sk->lambda; d.lam_ub = sk->lambda_ub; d.pv_raw = sk->pv_raw; d.b = sk->b; d.y = sk->y;
+      d.tptr = sk->sp.tptr; d.tmat = sk->sp.tmat; d.mapped = sk->sp.mapped; d.tval = sk->sp.tval;
+      d.triu_nzval = sk->sp.triu_nzval; d.nzval = sk->sp.nzval;
+      d.yb = a.out + q.nev + 2;
+      d.y_copy = q.y_out ? reinterpret_cast<double*>(dev + q.y_off) : nullptr;
+      dargs[k] = d;
+    }
     double* st = reinterpret_cast<double*>(tab.data() + q.v0_off);   // the caller's start vector, or sdplr_hip_S_eigval's fixed one
-    if (x.v0) std::copy(x.v0, x.v0 + n, st);
+    if (q.v0) std::copy(q.v0, q.v0 + n, st);
     else { unsigned long long z = 0x9E3779B97F4A7C15ull; for (long long i = 0; i < n; i++) { z = z * 6364136223846793005ull + 1442695040888963407ull; st[i] = (double)(z >> 11) / 9007199254740992.0 - 0.5; } }
   }
   if ((rc = h2d_copy(s, dev, tab.data(), tab_bytes))) return rc;
-  std::vector<char> res(tab_bytes - st_beg);
+  std::vector<char> res(res_end - st_beg);
+  if (dual) {   // y, S.nzval and ⟨y, b⟩ of every row: one grid ahead of the eigensolver's
+    k_dual_hp_prologue<<<(unsigned int)B, SDPLR_RS_NT, 0, s->stream>>>(reinterpret_cast<const DualHpArgs*>(dev + dh_off));
+    HIPCK(s, hipGetLastError());
+  }
   RS_SET_ATTR(k_eig_resident_batch);
   // every launch runs ≤ cap cycles of each unfinished instance; a finished one leaves its block at once
   long long most = 1;
-  for (const EigBatchRow& q : rows) most = std::max<long long>(most, (long long)((it[q.item].maxiter + cap - 1) / cap));
+  for (const EigBatchRow& q : rows) most = std::max<long long>(most, (long long)((q.maxiter + cap - 1) / cap));
   bool all_done = false;
   for (long long launch = 0; launch <= most && !all_done; launch++) {
     k_eig_resident_batch<<<(unsigned int)B, SDPLR_RS_NT, lds, s->stream>>>(reinterpret_cast<const EigResArgs*>(dev));
@@ -5525,11 +5622,12 @@ int eig_batch_shared(sdplr_hip_eig_item* it, std::vector<EigBatchRow>& rows) {
   }
   if (!all_done) return fail(s, SDPLR_ERR_HIP, "batch_S_eigval: an instance did not finish within its cycle budget");
   for (const EigBatchRow& q : rows) {
-    sdplr_hip_eig_item& x = it[q.item];
     const double* o = reinterpret_cast<const double*>(res.data() + (q.st_off - st_beg)) + EIG_ST_THETA + q.m;
-    for (int64_t i = 0; i < x.nev; i++) x.evals[i] = o[i];
-    x.n_matvec = (int64_t)o[x.nev];
-    x.n_converged = (int64_t)o[x.nev + 1];
+    for (int64_t i = 0; i < q.nev; i++) q.evals[i] = o[i];
+    *q.n_matvec = (int64_t)o[q.nev];
+    *q.n_converged = (int64_t)o[q.nev + 1];
+    if (dual) *q.yb = o[q.nev + 2];
+    if (q.y_out) memcpy(q.y_out, res.data() + (q.y_off - st_beg), (size_t)(q.s->m + 1) * sizeof(double));
   }
   return SDPLR_OK;
 }
@@ -5549,32 +5647,23 @@ int32_t sdplr_hip_batch_S_eigval(int32_t count, sdplr_hip_eig_item* it) {
     if (!batch_one_device(hs, &dev)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_S_eigval: the handles live on different devices");
     for (int i = 0; i < count; i++) { it[i].status = SDPLR_ERR_UNSERVED; it[i].route = 0; }
     ApiShared api_guard(dev);
-    long long nmax = SDPLR_EIG_BATCH_NMAX;
-    if (const char* e = getenv("SDPLR_HIP_BATCH_EIG_NMAX")) nmax = std::max(0LL, std::min(nmax, atoll(e)));
-    const char* off_env = getenv("SDPLR_HIP_NO_BATCH_EIG");
-    const bool off = off_env != nullptr && atoi(off_env) != 0;
+    const EigBatchEnv env;
     std::vector<EigBatchRow> rows;
     for (int i = 0; i < count; i++) {
-      const sdplr_hip_eig_item& q = it[i];
+      sdplr_hip_eig_item& q = it[i];
       S* s = q.s;
-      // whatever sdplr_hip_S_eigval would refuse goes to that call, which reports the item's status
-      bool ok = !off && s && s->finalized && q.evals && q.nev >= 1 && q.nev <= s->n && (q.which == 0 || q.which == 1) && q.maxiter >= 1 &&
-                rs_route_open(s) && s->have_sparse && s->lr.ST <= SDPLR_LRMAX && s->n <= nmax;
       int m = 0;
       bool ylds = false;
-      if (ok) {   // sdplr_hip_S_eigval's basis size
-        const int64_t n = s->n;
-        m = (int)std::min<int64_t>(n, std::max<int64_t>(q.ncv > 0 ? q.ncv : 100, std::min<int64_t>(n, 2 * q.nev + 1)));
-        if (m > 256) m = 256;
-        ok = q.nev <= m && (size_t)eig_rs_lds_doubles(n, m, false) * sizeof(double) <= RS_LDS_MAX;
-        ylds = ok && (size_t)eig_rs_lds_doubles(n, m, true) * sizeof(double) <= RS_LDS_MAX;
+      if (!eig_batch_takes(env, s, q.nev, q.which, q.ncv, q.maxiter, q.evals != nullptr, &m, &ylds) || eig_batch_prepare(s) != SDPLR_OK) {
+        single.push_back(i);
+        continue;
       }
-      if (!ok || eig_batch_prepare(s) != SDPLR_OK) { single.push_back(i); continue; }
-      rows.push_back(EigBatchRow{i, m, ylds, 0, 0, 0, 0});
+      rows.push_back(EigBatchRow{i, m, ylds, s, q.nev, q.which, q.tol, q.maxiter, q.v0, q.evals, &q.n_matvec, &q.n_converged,
+                                 nullptr, nullptr, 0, 0, 0, 0, 0});
     }
     if (!rows.empty()) {
-      const int rc = eig_batch_shared(it, rows);
-      S* lead = it[rows[0].item].s;
+      const int rc = eig_batch_shared(rows, false);
+      S* lead = rows[0].s;
       for (const EigBatchRow& q : rows) {
         sdplr_hip_eig_item& x = it[q.item];
         x.status = rc;
@@ -5586,6 +5675,59 @@ int32_t sdplr_hip_batch_S_eigval(int32_t count, sdplr_hip_eig_item* it) {
   run_singles(single, [&](int i) {
     sdplr_hip_eig_item& q = it[i];
     q.status = sdplr_hip_S_eigval(q.s, q.nev, q.which, q.ncv, q.tol, q.maxiter, q.v0, q.evals, &q.n_matvec, &q.n_converged);
+  });
+  for (int i = 0; i < count; i++) if (it[i].status) return it[i].status;
+  return SDPLR_OK;
+}
+
+int32_t sdplr_hip_batch_dual_obj_hp(int32_t count, sdplr_hip_dual_hp_item* it) {
+  if (count < 0 || (count > 0 && !it)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_dual_obj_hp: bad args");
+  if (count == 0) return SDPLR_OK;   // (nothing to serve, with or without a device)
+  if (have_device() <= 0) return fail(nullptr, SDPLR_ERR_NO_DEVICE, "no usable HIP device (libsdplr_hip has no CPU fallback)");
+  std::vector<int> single;
+  {
+    std::vector<const S*> hs;
+    for (int i = 0; i < count; i++) hs.push_back(it[i].s);
+    if (!batch_handles_distinct(hs)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_dual_obj_hp: a handle appears twice");   // (before any handle is dereferenced or any item written)
+    int dev = -1;
+    if (!batch_one_device(hs, &dev)) return fail(nullptr, SDPLR_ERR_INVALID_ARG, "batch_dual_obj_hp: the handles live on different devices");
+    for (int i = 0; i < count; i++) { it[i].status = SDPLR_ERR_UNSERVED; it[i].route = 0; }
+    ApiShared api_guard(dev);
+    const EigBatchEnv env;
+    std::vector<EigBatchRow> rows;
+    for (int i = 0; i < count; i++) {
+      sdplr_hip_dual_hp_item& q = it[i];
+      S* s = q.s;
+      int m = 0;
+      bool ylds = false;
+      if (!eig_batch_takes(env, s, 1, 0, q.ncv, q.maxiter, true, &m, &ylds)) { single.push_back(i); continue; }
+      // what the dual bound's entry points ask of a handle (NEED_FINAL_RW_KEEP_HISTORY): the prologue and the eigensolver
+      // touch y and S alone, nothing of the factor arena
+      s->hc_valid = false;
+      s->G_consistent = false;
+      rows.push_back(EigBatchRow{i, m, ylds, s, 1, 0, q.tol, q.maxiter, q.v0, &q.mineig, &q.n_matvec, &q.n_converged,
+                                 &q.dual_value, q.y_out, 0, 0, 0, 0, 0});
+    }
+    if (!rows.empty()) {
+      const int rc = eig_batch_shared(rows, true);
+      S* lead = rows[0].s;
+      for (const EigBatchRow& q : rows) {
+        sdplr_hip_dual_hp_item& x = it[q.item];
+        x.status = rc;
+        x.route = 1;
+        x.s->S_from_y = true;      // y is the bound's …
+        x.s->S_stale = rc != 0;    // … and S is assembled from it (after a failed call: by whoever reads it next)
+        if (rc) { if (x.s != lead) x.s->err = lead->err; continue; }
+        x.s->st_rs_shared++;
+        x.dual_value = -x.dual_value + x.trace_bound * std::min(x.mineig, 0.0);   // :412 (the prologue left ⟨y, b⟩ there)
+      }
+    }
+  }
+  run_singles(single, [&](int i) {
+    sdplr_hip_dual_hp_item& q = it[i];
+    if (!q.s) { q.status = SDPLR_ERR_INVALID_ARG; return; }
+    q.status = sdplr_hip_dual_obj_hp(q.s, q.trace_bound, q.ncv, q.tol, q.maxiter, q.v0, &q.dual_value, &q.mineig, &q.n_matvec, &q.n_converged);
+    if (!q.status && q.y_out) q.status = sdplr_hip_get_vec(q.s, SDPLR_V_Y, q.y_out, q.s->m + 1);
   });
   for (int i = 0; i < count; i++) if (it[i].status) return it[i].status;
   return SDPLR_OK;

@@ -151,6 +151,15 @@ def _print_row(config, majoriter, localiter, iter_, L, obj, σ, gtol, ptol, gnor
 REQ_FG, REQ_MAJOR, REQ_INNER, REQ_DUAL = "fg", "major_iteration", "inner_loop", "dual_obj"
 # … and the eigensolve of DIMACS_errors (eval_DIMACS_errs): (REQ_EIG, nev, which, ncv, tol, maxiter, v0) → (evals, matvecs, nconv)
 REQ_EIG = "S_eigval"
+# … and the high-precision dual bound (eigval_highprecision, src/coreop.jl:389-400):
+# (REQ_DUAL_HP, trace_bound, ncv, tol, maxiter, v0) → (dual_value, mineig, var.y if the driver already has it — the batched call does)
+REQ_DUAL_HP = "dual_obj_hp"
+
+
+def warn_unconverged(nconv: int, nevs: int = 1):
+    """SDP_S_eigval's warning (the cycle budget ran out before ``nevs`` Ritz values passed ARPACK's test)."""
+    if nconv < nevs:
+        print(f"Warning: SDP_S_eigval: {nconv} of {nevs} eigenvalues converged.", file=sys.stderr)
 
 
 def serve(var: DeviceSolver, req: tuple) -> tuple:
@@ -166,6 +175,19 @@ def serve(var: DeviceSolver, req: tuple) -> tuple:
         return var.dual_obj(*args) + (None,)      # (third: var.y if the driver already has it — the batched call does)
     if kind == REQ_EIG:
         return var.S_eigval(*args)
+    if kind == REQ_DUAL_HP:
+        trace_bound, ncv, tol, maxiter, v0 = args
+        if getattr(var.abi, "has_dual_hp", False):
+            dual_value, ev, _matvecs, nconv = var.dual_obj_hp(trace_bound, ncv, tol, maxiter, v0)
+            warn_unconverged(nconv)
+            return dual_value, ev, None
+        # an ABI without the entry point (the CPU checker's): the same bound step by step from the host
+        m = var.m
+        var.y = np.concatenate([-np.minimum(var.λ_ub, var.λ - var.σ * var.primal_vio_raw[:m]), [1.0]])
+        var.At_preprocess()
+        ev = SDP_S_eigval(var, 1, True, which="SA", ncv=ncv, tol=tol, maxiter=maxiter, v0=v0)[0]
+        dual_value = float(-(var.y[:m] @ var.b) + trace_bound * min(ev, 0.0))
+        return dual_value, ev, None
     raise ValueError(kind)
 
 
@@ -286,12 +308,8 @@ def sdplr_steps(data: SDPData, var: DeviceSolver, config: BurerMonteiroConfig, n
             t0 = time.time()
             v0 = rng.standard_normal(n)                         # replaces randn, coreop.jl:473
             y_now = None
-            if config.eigval_highprecision:                     # coreop.jl:389-400
-                var.y = np.concatenate([-np.minimum(var.λ_ub, var.λ - σ_now * var.primal_vio_raw[:m]), [1.0]])
-                var.At_preprocess()
-                ev = SDP_S_eigval(var, 1, True, which="SA", ncv=min(100, n), tol=1e-6, maxiter=1000000,
-                                  v0=v0)[0]
-                dual_value = float(-(var.y[:m] @ data.b) + config.prior_trace_bound * min(ev, 0.0))
+            if config.eigval_highprecision:                     # coreop.jl:389-400: copy2y, 𝒜t_preprocess!, SDP_S_eigval, :412
+                dual_value, _ev, y_now = yield (REQ_DUAL_HP, config.prior_trace_bound, min(100, n), 1e-6, 100000, v0)
             else:
                 dual_value, _, y_now = yield (REQ_DUAL, config.prior_trace_bound, iter_, v0)     # :314
             if dual_value > max_dual_value:                     # :324-327
