@@ -942,6 +942,26 @@ def linesearch_c(m: int) -> float:
     return 2.0 * (int(np.ceil(np.log2(max(m, 2)))) + 12)
 
 
+def commit_check(solver, pv_raw0, alpha, m: int) -> dict:
+    """The commit of either line search (:118-124 / :184-188) is a kernel of its own that reads the A_RD and A_DD the call
+    left: pv_raw + α(α·A_DD + A_RD) of THOSE vectors (themselves held to their references) in long double, to 4 ulp of its term
+    magnitudes; V_PV is its max with the lower bounds and S_OBJ its last entry, to the same.  → commit (error/bound) and the
+    exact properties obj_is_last, pv_is_raw."""
+    a = LD(alpha)
+    ard, add = _ld(solver.A_RD), _ld(solver.A_DD)
+    want = _ld(pv_raw0) + a * (a * add + ard)
+    tol = 4 * U53 * (np.abs(_ld(pv_raw0)) + a * (a * np.abs(add) + np.abs(ard)))
+    pv = solver.primal_vio_raw
+    lb = _ld(solver.primal_vio_lb)
+    errs = np.concatenate([np.abs(_ld(pv) - want), np.abs(_ld(solver.primal_vio) - np.maximum(want[:m], lb)),
+                           [abs(LD(solver.obj) - want[m])]])
+    tols = np.concatenate([tol, tol[:m], [tol[m]]])
+    ok = tols > 0
+    assert np.all(errs[~ok] == 0)
+    return dict(commit=float(np.max(errs[ok] / tols[ok])), obj_is_last=bool(solver.obj == pv[m]),
+                pv_is_raw=bool(np.array_equal(solver.primal_vio, np.maximum(pv[:m], solver.primal_vio_lb))))
+
+
 def check_linesearch_call(base: dict, st: dict, solver) -> dict:
     """Check 4 on one state and one handle (state applied, linesearch(α_max) run here).  → error/bound ratios
     (A_RD, A_DD, L, opt, commit) and the exact properties as booleans; nothing is asserted here."""
@@ -966,23 +986,7 @@ def check_linesearch_call(base: dict, st: dict, solver) -> dict:
     out["opt"] = float((f_at - mn["fmin"]) / (2 * cc * U53 * mn["T"](st["amax"])))
     out["inside"] = bool(0.0 <= alpha <= st["amax"])
     out["alpha"], out["alpha_hp"] = alpha, float(mn["alpha"])
-    # the commit (:118-124) is a kernel of its own that reads the A_RD and A_DD the call left: pv_raw + α(α·A_DD + A_RD) of
-    # THOSE vectors (themselves held to quartic_hp above) in long double, to 4 ulp of its term magnitudes; V_PV is its
-    # max with the lower bounds and S_OBJ its last entry, to the same
-    a = LD(alpha)
-    ard, add = _ld(solver.A_RD), _ld(solver.A_DD)
-    want = _ld(st["pv_raw"]) + a * (a * add + ard)
-    tol = 4 * U53 * (np.abs(_ld(st["pv_raw"])) + a * (a * np.abs(add) + np.abs(ard)))
-    pv = solver.primal_vio_raw
-    lb = _ld(solver.primal_vio_lb)
-    errs = np.concatenate([np.abs(_ld(pv) - want), np.abs(_ld(solver.primal_vio) - np.maximum(want[:m], lb)),
-                           [abs(LD(solver.obj) - want[m])]])
-    tols = np.concatenate([tol, tol[:m], [tol[m]]])
-    ok = tols > 0
-    assert np.all(errs[~ok] == 0)
-    out["commit"] = float(np.max(errs[ok] / tols[ok]))
-    out["obj_is_last"] = bool(solver.obj == pv[m])
-    out["pv_is_raw"] = bool(np.array_equal(solver.primal_vio, np.maximum(pv[:m], solver.primal_vio_lb)))
+    out.update(commit_check(solver, st["pv_raw"], alpha, m))
     return out
 
 
@@ -1039,7 +1043,7 @@ def split_matrices(C, As):
     return (cat(Is, np.int64), cat(Js, np.int64), cat(Vs, np.float64), cat(Os, np.int64)), lows
 
 
-def A_pair_hp(C, As, U, V) -> dict:
+def A_pair_hp(C, As, U, V, split=None) -> dict:
     """q[i] = ⟨Aᵢ, (UVᵀ + VUᵀ)/2⟩ for every matrix (cost last) above FP64, entry by entry (a low-rank one as Σ_c d_c⟨Bᵀ_cU,
     Bᵀ_cV⟩), never an n×n array; mag[i] the sum of the magnitudes of its elementary products, Σ|a_jk|(⟨|U_j|,|V_k|⟩ +
     ⟨|V_j|,|U_k|⟩)/2; depth[i] the roundings an FP64 evaluation makes on the way to one output in ANY summation order:
@@ -1049,7 +1053,7 @@ def A_pair_hp(C, As, U, V) -> dict:
     same = U64 is V64 or np.array_equal(U64, V64)
     k = 1 if same else 2
     n, r = U64.shape
-    (I, J, W, own), lows = split_matrices(C, As)
+    (I, J, W, own), lows = split or split_matrices(C, As)
     M = len(As) + 1
     aU, aV = np.abs(U64), np.abs(V64)
     if same:
@@ -1107,12 +1111,12 @@ def ytilde_from(pv_raw, lam, lam_ub, sigma) -> dict:
     return dict(yt=np.minimum(ub, t), free=t, ub=ub, bound=bound, near=near, capped=np.asarray(t > ub))
 
 
-def device_pattern(C, As) -> dict:
+def device_pattern(C, As, split=None) -> dict:
     """The pattern S is kept on (src/preprocess.jl:24-169), rebuilt here from the matrices' own entries: the union of the sparse
     matrices' upper-triangular entries in CSC order (V_TRIU_S_NZVAL), the union of all their entries in CSC order (V_S_NZVAL),
     each full entry's position (min, max) in the upper one, and per aggregated entry its position and owner."""
     n = C.shape[0]
-    (I, J, W, own), lows = split_matrices(C, As)
+    (I, J, W, own), lows = split or split_matrices(C, As)
     up = I <= J
     keyT = np.unique(J[up] * n + I[up])
     keyF = np.unique(J * n + I)
@@ -1182,3 +1186,280 @@ def worst_ratio(got, want, bound) -> float:
         ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.where(err == 0, 0.0, np.inf))
     ratio = np.where(np.isnan(ratio), np.inf, ratio)
     return float(np.max(ratio))
+
+
+# ---- the loop routes, shared by tests/test_gpu_direction_linesearch.py and tests/test_gpu_armijo.py --------------------------
+LOOP_TOGGLES = ["SDPLR_HIP_NO_RING", "SDPLR_HIP_NO_UPDFUSE", "SDPLR_HIP_DOT_DESCENT", "SDPLR_HIP_NO_FAST", "SDPLR_HIP_NO_FAST2",
+                "SDPLR_HIP_NO_GRAPH", "SDPLR_HIP_TEAM", "SDPLR_HIP_NO_RESIDENT", "SDPLR_HIP_GRAPH_ITERS", "SDPLR_HIP_NO_LRFUSE",
+                "SDPLR_HIP_NO_GROUP_LAUNCH"]
+# route → (environment, SDPLR_HIP_FORCE_GRAPH kept: the suite's default, which keeps the resident loop out)
+LOOP_ROUTES = {
+    "graph": ({"SDPLR_HIP_GRAPH_ITERS": "2"}, True),           # (batches shorter than k: several replays)
+    "eager": ({"SDPLR_HIP_NO_GRAPH": "1"}, True),
+    "stored": ({"SDPLR_HIP_NO_RING": "1"}, True),
+    "no_updfuse": ({"SDPLR_HIP_NO_UPDFUSE": "1"}, True),
+    "dot_descent": ({"SDPLR_HIP_DOT_DESCENT": "1"}, True),
+    "no_fast": ({"SDPLR_HIP_NO_FAST": "1"}, True),
+    "no_fast2": ({"SDPLR_HIP_NO_FAST2": "1"}, True),
+    "no_lrfuse": ({"SDPLR_HIP_NO_LRFUSE": "1"}, True),
+    "resident_team1": ({"SDPLR_HIP_TEAM": "1"}, False),
+    "resident_team3": ({"SDPLR_HIP_TEAM": "3"}, False),
+    "resident_batch": ({}, False),                             # three instances in one sdplr_hip_batch_major_iteration
+    "group": ({}, True),                                       # the same call on the edge path: the group launch
+}
+RESIDENT_FAMILIES = ("maxcut", "maxcut300", "minimum_bisection", "cutnorm")   # (the edge path and low-rank terms stay on launches)
+
+
+def set_route(monkeypatch, route):
+    env, force_graph = LOOP_ROUTES[route]
+    for k in LOOP_TOGGLES:
+        monkeypatch.delenv(k, raising=False)
+    if force_graph:
+        monkeypatch.setenv("SDPLR_HIP_FORCE_GRAPH", "1")
+    else:
+        monkeypatch.delenv("SDPLR_HIP_FORCE_GRAPH", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def assert_route(route, family, r, h, st, armijo=False):
+    """Which route ran, from stats(): the resident loop (one workgroup, h ≤ 4: above that the library itself goes back to
+    launches), its shared batch launch, the group launch (h ≤ 4), graph replays or eager batches, the ring form (taken at
+    n = 300, r = 8 and at n = 12, r = 32, under graph and eager, h ≤ 4 — not at n = 12, r = 3) and the P-less step kernel, which the fused-update, dot-descent and
+    NO_FAST/NO_FAST2 toggles — having no counter of their own — switch off together with the ring.
+    armijo: a loop with inequality data.  The resident loop, the group launch, the ring form and the P-less step kernel all
+    refuse it, whatever the route asks for: every iteration is a graph replay or an eager batch of launches."""
+    tag = (route, family, r, h, st)
+    if armijo:
+        assert st["resident_loops"] == 0 and st["resident_shared_launches"] == 0 and st["group_launch_loops"] == 0, tag
+        assert st["ring_history_loops"] == 0 and st["p_less_loops"] == 0 and st["inner_iterations"] >= 1, tag
+        if route == "graph":
+            assert st["graph_batches"] >= 1, tag
+        if route == "eager":
+            assert st["graph_batches"] == 0 and st["eager_batches"] >= 1, tag
+        return
+    resident = route.startswith("resident") and family in RESIDENT_FAMILIES and h <= 4
+    if resident:
+        assert st["resident_loops"] >= 1 and st["graph_batches"] == 0 and st["eager_batches"] == 0, tag
+        assert (st["resident_shared_launches"] >= 1) == (route == "resident_batch"), tag
+        return
+    assert st["resident_loops"] == 0 and st["resident_shared_launches"] == 0, tag
+    if route == "group" and h <= 4:        # (h = 5: the library runs the batch's items one by one)
+        assert st["group_launch_loops"] >= 1 and family == "lovasz_theta", tag
+        return
+    assert st["group_launch_loops"] == 0, tag
+    if route == "graph":
+        assert st["graph_batches"] >= 2, tag
+    if route == "eager":
+        assert st["graph_batches"] == 0 and st["eager_batches"] >= 1, tag
+    ring = (family == "maxcut300" or (family == "maxcut" and r == 32)) and route in ("graph", "eager", "no_lrfuse") and h <= 4
+    if not (family == "maxcut" and r == 32 and h > 4):        # (not measured: left open rather than guessed)
+        assert (st["ring_history_loops"] >= 1) == ring, tag
+    if route in ("no_updfuse", "dot_descent", "no_fast", "no_fast2"):
+        assert st["p_less_loops"] == 0, tag
+    elif family in ("maxcut", "maxcut300") and r != 32 and h <= 4 and not route.startswith("resident"):
+        assert st["p_less_loops"] >= 1, tag
+
+
+# ---- Armijo backtracking above FP64 (tests/test_armijo_reference.py, tests/test_gpu_armijo.py) -------------------------------
+ARMIJO_K = 50            # halvings at the most (src/linesearch.jl:177)
+
+
+def _adot(a, b):
+    """⟨a, b⟩ above FP64: of long doubles where numpy has them, else of the doubles' exact products (_hp_dot)."""
+    return np.dot(a, b) if WIDE else _hp_dot(a, b)
+
+
+def armijo_hp(pv_raw, obj, lam, lam_ub, y, sigma, alpha_max, A_RD, A_DD) -> dict:
+    """src/linesearch.jl:139-191 above FP64, from the A_RD and A_DD a call left (both of length m + 1, the objective's entry
+    last; A_RD with its ×2).  For k = 0 … 50, α_k = α_max/2^k (exact halvings):
+      L[k]      = obj + α_k·p1 + α_k²·p2 + Σ_i (λ̃_i(α_k)² − λ_i²)/(2σ),  λ̃_i(α) = min(λ_ub_i, λ_i − σ·g_i(α)),
+                  g_i(α) = pv_raw_i + α·A_RD_i + α²·A_DD_i                                               (eval_AL, :157-165)
+      L0, slope = ℒ(0) and p1 + ⟨y[:m], A_RD[:m]⟩                                                         (:167, :171)
+      margin[k] = L0 + 1e-4·α_k·slope − L[k]: the step is accepted at the first k with margin ≥ 0          (:173-181)
+      T[k]      = |obj| + α_k|p1| + α_k²|p2| + Σ_i [(λ̃_i² + λ_i²)/(2σ) + |λ̃_i|·(|λ_i|/σ + |g0_i| + α_k|q1_i| + α_k²|q2_i|)]
+                  — the sum's own terms, and to first order what rounding g_i and λ − σ·g_i does inside the square; the latter
+                  is zero on a row where the cap wins (there λ̃ = λ_ub exactly).  T0 the same at α = 0.
+      T_slope   = |p1| + Σ|y_i·q1_i|
+      tau[k]    = c·u·(T0 + T[k] + 1e-4·α_k·T_slope),  c = linesearch_c(m): what an FP64 evaluation of margin[k] may be off by
+      k_hp      = the first k with margin ≥ 0, or 50
+      decided   = |margin[k]| > 10·tau[k] for every k ≤ k_hp (k < 50: after the 50th halving nothing is tested any more)
+      capped[k] = the rows on which the cap wins at α_k.
+    Without a wider long double the sums are math.fsum over exact products of doubles (the rows' own values are then formed
+    in double)."""
+    m = len(lam)
+    g0, q1, q2 = _ld(pv_raw)[:m], _ld(A_RD)[:m], _ld(A_DD)[:m]
+    p1, p2 = LD(np.float64(A_RD[m])), LD(np.float64(A_DD[m]))
+    lam_, ub, sg, ob = _ld(lam), _ld(lam_ub), LD(np.float64(sigma)), LD(np.float64(obj))
+    l2 = _adot(lam_, lam_)
+    ag0, aq1, aq2, al = np.abs(g0), np.abs(q1), np.abs(q2), np.abs(lam_) / sg
+    one = np.ones(m, dtype=LD)
+
+    def at(a):
+        free = lam_ - sg * (g0 + a * q1 + a * a * q2)
+        cap = np.asarray(free > ub)
+        lt = np.where(cap, ub, free)
+        t2 = _adot(lt, lt)
+        sens = np.where(cap, 0, np.abs(lt) * (al + ag0 + a * aq1 + a * a * aq2))
+        L = ob + a * p1 + a * a * p2 + (t2 - l2) / (2 * sg)
+        T = abs(ob) + a * abs(p1) + a * a * abs(p2) + (t2 + l2) / (2 * sg) + _adot(sens, one)
+        return L, T, cap
+
+    alphas = np.array([LD(np.float64(alpha_max)) * LD(2.0) ** -k for k in range(ARMIJO_K + 1)], dtype=LD)
+    L0, T0, cap0 = at(LD(0))
+    yl = _ld(y)[:m]
+    slope, T_slope = p1 + _adot(yl, q1), abs(p1) + _adot(np.abs(yl), aq1)
+    vals = [at(a) for a in alphas]
+    L, T = np.array([v[0] for v in vals], dtype=LD), np.array([v[1] for v in vals], dtype=LD)
+    c = linesearch_c(m)
+    c1 = LD(np.float64(1e-4))
+    margin = L0 + c1 * alphas * slope - L
+    tau = c * LD(U53) * (T0 + T + c1 * alphas * T_slope)
+    acc = np.flatnonzero(margin[:ARMIJO_K] >= 0)
+    k_hp = int(acc[0]) if acc.size else ARMIJO_K
+    upto = min(k_hp, ARMIJO_K - 1)
+    return dict(alpha=np.asarray(alphas, dtype=np.float64), L=L, T=T, L0=L0, T0=T0, slope=slope, T_slope=T_slope, margin=margin,
+                tau=tau, k_hp=k_hp, c=c, decided=bool(np.all(np.abs(margin[:upto + 1]) > 10 * tau[:upto + 1])),
+                capped=np.stack([v[2] for v in vals]), capped0=cap0)
+
+
+def armijo_k_of(alpha: float, alpha_max: float):
+    """k with alpha == α_max/2^k bit for bit, or None."""
+    for k in range(ARMIJO_K + 1):
+        if alpha == float(alpha_max) * 2.0 ** -k:
+            return k
+    return None
+
+
+def armijo_decision_ok(ref: dict, k_dev: int) -> bool:
+    """A device answer k_dev is right iff every k < k_dev has margin < τ (legitimately rejected) and k_dev = 50 or
+    margin[k_dev] ≥ −τ (legitimately accepted)."""
+    g, tau = ref["margin"], ref["tau"]
+    return bool(np.all(g[:k_dev] < tau[:k_dev]) and (k_dev == ARMIJO_K or g[k_dev] >= -tau[k_dev]))
+
+
+_ARM_CACHE = {}
+
+
+def armijo_base(n: int, m: int, r: int, seed: int = 0) -> dict:
+    """A problem of the Armijo tests with any row count m ≤ n(n+1)/2 + 1: the cost is a graph Laplacian on n vertices, row 0 an
+    equality with a full (unit) diagonal, rows 1 … m − 1 inequalities that are single symmetric entries (i, j), i ≤ j, drawn
+    without repetition, with seeded values and right-hand sides.  With it: a seeded Gaussian R (n×r) and λ, σ = 2, pv_raw and
+    obj the true ones at R above FP64, λ_ub by the recipe of fg_cases.case_inputs (+∞ on the equality row; the inequality rows
+    cycle through 0 and ½ and 1½ times λ − σv; λ moved strictly below λ_ub where it was above), y as g! leaves it, and G = 2·S(y)·R
+    above FP64 — the gradient of the capped ℒ, which hp_gradient's equality form is not.  Built once and left unchanged.  The
+    SDPData is handed over as one batch (no pass over m Python objects in its constructor)."""
+    key = (n, m, r, seed)
+    if key in _ARM_CACHE:
+        return _ARM_CACHE[key]
+    from sdplrplus_jl_amd.structs import SparseBatch
+    assert 1 <= m <= n * (n + 1) // 2 + 1
+    rng = np.random.Generator(np.random.PCG64(8800 + 131 * seed + m))
+    A = problems.gnp_graph(n, min(0.5, 6.0 / n), 500 + n + seed)
+    C = sp.csc_matrix(sp.diags(np.asarray(A.sum(axis=1)).ravel()) - A)
+    ju, iu = np.triu_indices(n)          # (row ≥ col of the transpose: every pair i ≤ j once)
+    pick = rng.choice(iu.size, size=m - 1, replace=False)
+    pi, pj = np.minimum(iu[pick], ju[pick]), np.maximum(iu[pick], ju[pick])
+    vals = rng.standard_normal(m - 1) * 2.0 ** rng.integers(-3, 4, size=m - 1)
+    As = [sj.SparseMatrixCOO(np.arange(n), np.arange(n), np.ones(n), n, n)]
+    for i, j, v in zip(pi.tolist(), pj.tolist(), vals.tolist()):
+        As.append(sj.SparseMatrixCOO([i], [i], [v], n, n) if i == j else sj.SparseMatrixCOO([i, j], [j, i], [v, v], n, n))
+    bs = rng.standard_normal(m)
+    ct = np.arange(m) > 0
+    split = split_matrices(C, As)
+    (I, J, V, own), _ = split
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(own, minlength=m + 1))]).astype(np.int64)
+    data = sj.SDPData.from_batch(C, bs, SparseBatch(n, ptr, I, J, V, np.arange(m + 1, dtype=np.int64)), [], ct)
+    pattern = device_pattern(C, As, split)
+    R = rng.standard_normal((n, r))
+    lam = rng.standard_normal(m)
+    sigma = LS_SIGMA
+    a = A_pair_hp(C, As, R, R, split)
+    pv = a["q"].copy()
+    pv[:m] -= _ld(bs)
+    pv_raw = np.asarray(pv, dtype=np.float64)
+    free = np.asarray(_ld(lam) - LD(sigma) * _ld(pv_raw)[:m], dtype=np.float64)
+    ub = np.full(m, np.inf)
+    q = np.flatnonzero(ct)
+    ub[q] = 0.0
+    ub[q[1::4]] = 0.5 * free[q[1::4]]
+    ub[q[3::4]] = 1.5 * free[q[3::4]]
+    with np.errstate(invalid="ignore"):
+        lam = np.where(lam > ub, ub - np.abs(ub) - 0.01, lam)
+    y = np.concatenate([-np.asarray(ytilde_from(pv_raw, lam, ub, sigma)["yt"], dtype=np.float64), [1.0]])
+    G = np.asarray(S_and_G_hp(C, As, y, R, pattern)["G"], dtype=np.float64)
+    out = dict(n=n, m=m, r=r, seed=seed, C=C, As=As, bs=bs, ct=ct, data=data, split=split, pattern=pattern, R=R, lam=lam, ub=ub,
+               sigma=sigma, pv_raw=pv_raw, obj=float(pv_raw[m]), G=G)
+    _ARM_CACHE[key] = out
+    return out
+
+
+def armijo_state(base: dict, t: float, amax: float, kind: str = "descent") -> dict:
+    """One state on armijo_base: D = fl(t·(−G)) (kind "descent"), fl(t·G) ("ascent": every trial step is rejected until the
+    margin drops below its own round-off — the exhaustion state) or 0 ("tie": ℒ(α) = ℒ(0) and the slope 0 for every α, accepted
+    at once by `≤`).  A block of inequality rows — the last min(16, ⌈#inequalities/4⌉) of them — gets
+    λ_ub_i = fl(λ_i − σ·g_i(α*)), α* = ¾·α_max/2^j with j cycling through k₀ − 1 … k₀ − 4 (not below 0), k₀ the step the search
+    accepts without this block: those rows sit ON the cap at a point strictly between the trial steps α_j and α_{j+1}, so they
+    change sides while the search backtracks past it (asserted above FP64 in tests/test_armijo_reference.py; an α* far above
+    the accepted step would put g_i(α*)² — growing as t⁴ — into ℒ(0) as a constant and drown every margin in its round-off).  y is then what g! leaves for that λ_ub.  Also the references of 𝒜(RDᵀ + DRᵀ) and 𝒜(DDᵀ)
+    above FP64 with their termwise magnitudes and depths (A_pair_hp)."""
+    C, As, R, G, m = base["C"], base["As"], base["R"], base["G"], base["m"]
+    D = {"descent": -t * G, "ascent": t * G, "tie": np.zeros_like(G)}[kind]
+    a1, a2 = A_pair_hp(C, As, R, D, base["split"]), A_pair_hp(C, As, D, D, base["split"])
+    lam, ub, sg = base["lam"], base["ub"].copy(), LD(base["sigma"])
+    ineq = np.flatnonzero(base["ct"])
+    cross = ineq[len(ineq) - min(16, -(-len(ineq) // 4)):] if len(ineq) and kind != "tie" else ineq[:0]
+    if cross.size:
+        ard, add = np.asarray(2 * a1["q"], dtype=np.float64), np.asarray(a2["q"], dtype=np.float64)
+        y0 = np.concatenate([-np.asarray(ytilde_from(base["pv_raw"], lam, ub, base["sigma"])["yt"], dtype=np.float64), [1.0]])
+        k0 = armijo_hp(base["pv_raw"], base["obj"], lam, ub, y0, base["sigma"], amax, ard, add)["k_hp"]
+        j = np.maximum(0, k0 - 1 - np.arange(cross.size) % 4)
+        astar = LD(np.float64(amax)) * LD(0.75) * LD(2.0) ** -j.astype(LD)
+        gi = _ld(base["pv_raw"])[cross] + astar * (2 * a1["q"][cross]) + astar * astar * a2["q"][cross]
+        ub[cross] = np.asarray(_ld(lam)[cross] - sg * gi, dtype=np.float64)
+    y = np.concatenate([-np.asarray(ytilde_from(base["pv_raw"], lam, ub, base["sigma"])["yt"], dtype=np.float64), [1.0]])
+    return dict(R=R, D=np.asarray(D, dtype=np.float64), lam=lam, ub=ub, y=y, pv_raw=base["pv_raw"].copy(), obj=base["obj"],
+                sigma=base["sigma"], t=t, amax=amax, kind=kind, cross=cross, a1=a1, a2=a2)
+
+
+def armijo_state_ref(st: dict) -> dict:
+    """armijo_hp on the state's own 𝒜 vectors above FP64 rounded to double: what the generator's claims are stated on."""
+    ard, add = np.asarray(2 * st["a1"]["q"], dtype=np.float64), np.asarray(st["a2"]["q"], dtype=np.float64)
+    return armijo_hp(st["pv_raw"], st["obj"], st["lam"], st["ub"], st["y"], st["sigma"], st["amax"], ard, add)
+
+
+def crossings(ref: dict, rows) -> int:
+    """Rows among `rows` that change sides of the cap between two consecutive trial steps k, k + 1 ≤ k_hp."""
+    cap = ref["capped"][:ref["k_hp"] + 1][:, rows]
+    return int(np.sum(np.any(cap[1:] != cap[:-1], axis=0))) if cap.shape[0] > 1 else 0
+
+
+def apply_armijo_state(s_, st: dict):
+    apply_linesearch_state(s_, st)
+    s_.λ_ub = st["ub"]
+    s_.y = st["y"]
+
+
+def check_armijo_call(base: dict, st: dict, solver) -> dict:
+    """One state on one handle (applied and linesearch_armijo(α_max) run here).  → error/bound ratios A_RD, A_DD (termwise against
+    A_pair_hp), L (ℒ against L[k_dev] of armijo_hp on the handle's own A_RD, A_DD, bound c·u·T[k_dev]), commit (commit_check), and
+    the exact properties: on_grid (α = α_max/2^k_dev bit for bit for some k_dev ≤ 50), decision_ok (armijo_decision_ok),
+    alpha_exact (a decided state: k_dev = k_hp), obj_is_last, pv_is_raw; with k_dev, k_hp, decided.  Nothing is asserted here."""
+    m = base["m"]
+    apply_armijo_state(solver, st)
+    alpha, L = solver.linesearch_armijo(st["amax"])
+    ard, add = solver.A_RD, solver.A_DD
+    a1, a2 = st["a1"], st["a2"]
+    out = dict(A_RD=worst_ratio(ard, 2 * a1["q"], a1["depth"] * LD(U53) * 2 * a1["mag"]),
+               A_DD=worst_ratio(add, a2["q"], a2["depth"] * LD(U53) * a2["mag"]))
+    ref = armijo_hp(st["pv_raw"], st["obj"], st["lam"], st["ub"], st["y"], st["sigma"], st["amax"], ard, add)
+    k = armijo_k_of(alpha, st["amax"])
+    out.update(alpha=alpha, k_dev=k, k_hp=ref["k_hp"], decided=ref["decided"], on_grid=k is not None, ref=ref)
+    if k is None:
+        out.update(L=np.inf, decision_ok=False, alpha_exact=False)
+    else:
+        out["L"] = worst_ratio([L], [ref["L"][k]], [ref["c"] * LD(U53) * ref["T"][k]])
+        out["decision_ok"] = armijo_decision_ok(ref, k)
+        out["alpha_exact"] = bool(k == ref["k_hp"]) if ref["decided"] else True
+    out.update(commit_check(solver, st["pv_raw"], alpha, m))
+    return out

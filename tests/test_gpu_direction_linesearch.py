@@ -164,66 +164,7 @@ from sdplrplus_jl_amd import cabi, problems                                     
 from helpers import (U53, direction_errors, history_snapshot, lanczos_instance, linesearch_c, loop_state_direction, poly_hp,  # noqa: E402
                      quartic_hp, quartic_min_hp)
 
-LOOP_TOGGLES = ["SDPLR_HIP_NO_RING", "SDPLR_HIP_NO_UPDFUSE", "SDPLR_HIP_DOT_DESCENT", "SDPLR_HIP_NO_FAST", "SDPLR_HIP_NO_FAST2",
-                "SDPLR_HIP_NO_GRAPH", "SDPLR_HIP_TEAM", "SDPLR_HIP_NO_RESIDENT", "SDPLR_HIP_GRAPH_ITERS", "SDPLR_HIP_NO_LRFUSE",
-                "SDPLR_HIP_NO_GROUP_LAUNCH"]
-# route → (environment, SDPLR_HIP_FORCE_GRAPH kept: the suite's default, which keeps the resident loop out)
-LOOP_ROUTES = {
-    "graph": ({"SDPLR_HIP_GRAPH_ITERS": "2"}, True),           # (batches shorter than k: several replays)
-    "eager": ({"SDPLR_HIP_NO_GRAPH": "1"}, True),
-    "stored": ({"SDPLR_HIP_NO_RING": "1"}, True),
-    "no_updfuse": ({"SDPLR_HIP_NO_UPDFUSE": "1"}, True),
-    "dot_descent": ({"SDPLR_HIP_DOT_DESCENT": "1"}, True),
-    "no_fast": ({"SDPLR_HIP_NO_FAST": "1"}, True),
-    "no_fast2": ({"SDPLR_HIP_NO_FAST2": "1"}, True),
-    "no_lrfuse": ({"SDPLR_HIP_NO_LRFUSE": "1"}, True),
-    "resident_team1": ({"SDPLR_HIP_TEAM": "1"}, False),
-    "resident_team3": ({"SDPLR_HIP_TEAM": "3"}, False),
-    "resident_batch": ({}, False),                             # three instances in one sdplr_hip_batch_major_iteration
-    "group": ({}, True),                                       # the same call on the edge path: the group launch
-}
-RESIDENT_FAMILIES = ("maxcut", "maxcut300", "minimum_bisection", "cutnorm")   # (the edge path and low-rank terms stay on launches)
-
-
-def _set_route(monkeypatch, route):
-    env, force_graph = LOOP_ROUTES[route]
-    for k in LOOP_TOGGLES:
-        monkeypatch.delenv(k, raising=False)
-    if force_graph:
-        monkeypatch.setenv("SDPLR_HIP_FORCE_GRAPH", "1")
-    else:
-        monkeypatch.delenv("SDPLR_HIP_FORCE_GRAPH", raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-
-
-def _assert_route(route, family, r, h, st):
-    """Which route ran, from stats(): the resident loop (one workgroup, h ≤ 4: above that the library itself goes back to
-    launches), its shared batch launch, the group launch (h ≤ 4), graph replays or eager batches, the ring form (taken at
-    n = 300, r = 8 and at n = 12, r = 32, under graph and eager, h ≤ 4 — not at n = 12, r = 3) and the P-less step kernel, which the fused-update, dot-descent and
-    NO_FAST/NO_FAST2 toggles — having no counter of their own — switch off together with the ring."""
-    tag = (route, family, r, h, st)
-    resident = route.startswith("resident") and family in RESIDENT_FAMILIES and h <= 4
-    if resident:
-        assert st["resident_loops"] >= 1 and st["graph_batches"] == 0 and st["eager_batches"] == 0, tag
-        assert (st["resident_shared_launches"] >= 1) == (route == "resident_batch"), tag
-        return
-    assert st["resident_loops"] == 0 and st["resident_shared_launches"] == 0, tag
-    if route == "group" and h <= 4:        # (h = 5: the library runs the batch's items one by one)
-        assert st["group_launch_loops"] >= 1 and family == "lovasz_theta", tag
-        return
-    assert st["group_launch_loops"] == 0, tag
-    if route == "graph":
-        assert st["graph_batches"] >= 2, tag
-    if route == "eager":
-        assert st["graph_batches"] == 0 and st["eager_batches"] >= 1, tag
-    ring = (family == "maxcut300" or (family == "maxcut" and r == 32)) and route in ("graph", "eager", "no_lrfuse") and h <= 4
-    if not (family == "maxcut" and r == 32 and h > 4):        # (not measured: left open rather than guessed)
-        assert (st["ring_history_loops"] >= 1) == ring, tag
-    if route in ("no_updfuse", "dot_descent", "no_fast", "no_fast2"):
-        assert st["p_less_loops"] == 0, tag
-    elif family in ("maxcut", "maxcut300") and r != 32 and h <= 4 and not route.startswith("resident"):
-        assert st["p_less_loops"] >= 1, tag
+from helpers import LOOP_ROUTES, RESIDENT_FAMILIES, assert_route as _assert_route, set_route as _set_route        # noqa: E402
 
 
 def _loop_datas(family, route):

@@ -9,7 +9,7 @@ import scipy.sparse as sp
 
 import sdplrplus_jl_amd as sj
 from sdplrplus_jl_amd import cabi, problems
-from helpers import (FAMILIES_EQ, GRID, S_dense, U53, lagrangian_dense, lanczos_tau, linesearch_c, make_data, make_solver,
+from helpers import (FAMILIES_EQ, GRID, S_dense, U53, armijo_hp, lagrangian_dense, lanczos_tau, linesearch_c, make_data, make_solver,
                      poly_hp, primal_vio_dense, quartic_hp, quartic_min_hp)
 
 pytestmark = pytest.mark.gpu
@@ -269,7 +269,25 @@ def test_armijo_decision_at_the_bound(hip_abi, oracle_abi):
     g.close(); o.close()
 
 
-@pytest.mark.parametrize("family", ["maxcut", "lovasz_theta"])
+def armijo_steps_agree_where_decided(g, o, normC, normb, iters):
+    """Both handles from their common start, one iteration per call: wherever the oracle's own state before an iteration is
+    decided above FP64 (helpers.armijo_hp on what it held before the call and the A_RD, A_DD its line search left: every margin
+    up to the accepted step more than ten times its round-off), the device accepts the very same step.  → (decided, all)."""
+    sg, so = g.fg(normC, normb), o.fg(normC, normb)
+    decided = 0
+    for it in range(iters):
+        pre = (o.primal_vio_raw, o.obj, o.λ, o.λ_ub, o.y, o.σ)
+        rg = g.inner_loop(normC, normb, True, True, True, 0.0, -1e300, 1, 0.0, *sg)
+        ro = o.inner_loop(normC, normb, True, True, True, 0.0, -1e300, 1, 0.0, *so)
+        assert rg[4] == ro[4] == 1
+        if armijo_hp(*pre, 1.0, o.A_RD, o.A_DD)["decided"]:
+            decided += 1
+            assert rg[3] == ro[3], (it, rg[3], ro[3])
+        sg, so = rg[:3], ro[:3]
+    return decided, iters
+
+
+@pytest.mark.parametrize("family", ["maxcut", "lovasz_theta", "ineq_0.05"])
 @pytest.mark.parametrize("h", [1, 2, 3, 5, 8])
 def test_inner_loop_trajectory_over_history_lengths(hip_abi, oracle_abi, family, h):
     """numlbfgsvecs ≠ 4 inside the device-driven loop: the seam kernel's register form (h ≤ 4) and its general form,
@@ -290,6 +308,11 @@ def test_inner_loop_trajectory_over_history_lengths(hip_abi, oracle_abi, family,
     assert g.get_scalar(cabi.S_LBFGS_LATEST) == o.get_scalar(cabi.S_LBFGS_LATEST)
     assert np.allclose(g.get_vec(cabi.V_LBFGS_RHO), o.get_vec(cabi.V_LBFGS_RHO), rtol=1e-6)
     g.close(); o.close()
+    if arm:     # an Armijo flip is decided by the margin, not by luck: the same iterations one call at a time
+        g, o = pair(hip_abi, oracle_abi, data, 3, 7, h=h)
+        decided, _ = armijo_steps_agree_where_decided(g, o, normC, normb, k)
+        assert decided >= 1
+        g.close(); o.close()
 
 
 @pytest.mark.parametrize("family", ["maxcut", "minimum_bisection", "lovasz_theta", "mu_conductance_0.05", "ineq_0.05"])
@@ -674,6 +697,11 @@ def test_code_paths_agree(hip_abi, oracle_abi, family, toggles, monkeypatch):
     scale = np.array([max(abs(st0[0]), abs(base[0])), max(st0[1], base[1]), max(st0[2], base[2])])
     assert np.all(np.abs(np.array(base[:3]) - np.array(alt[:3])) <= (1e-6 if armijo else 1e-9) * scale) and rel(Rb, Ra) < tolR
     assert np.all(np.abs(np.array(base[:3]) - np.array(ora[:3])) <= (1e-6 if armijo else 1e-8) * scale) and rel(Rb, Ro) < 10 * tolR
+    if armijo:  # with the path switched off, one iteration per call: where the oracle's state is decided above FP64, the same step
+        g, o = pair(hip_abi, oracle_abi, data, r, 21)
+        decided, _ = armijo_steps_agree_where_decided(g, o, normC, normb, iters)
+        assert decided >= 1
+        g.close(); o.close()
 
 
 def test_step_kernel_without_P_carries_G_forward(hip_abi, oracle_abi, monkeypatch):
